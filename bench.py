@@ -3,7 +3,9 @@
 (BASELINE.json configs[1]); one "step" = one poem_head_forward over one resident synthetic batch + the metric feed +
 the 16-byte metric all-reduce.  Prints ONE JSON line on rank 0 (contract in the task statement / DESIGN.md).
 
-  python bench.py                       # 1 GPU, default steps
+  python bench.py                       # 1 GPU, default steps: the headline line only
+  python bench.py --full                # + roofline, opt-in / A-B legs, extra configs, E2E scopes, CPU / eager baselines
+  python bench.py --dump-outputs DIR    # + the last timed step's outputs as DIR/<name>.npy
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 """
@@ -429,6 +431,22 @@ def to_dev(item, dev):
     return f.to(dev), m, r.to(dev)
 
 
+DUMP_LIMIT_BYTES = 60 << 20     # --dump-outputs stays under 64 MB in all
+
+
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: each host tensor of ``arrays`` (name -> tensor) as ``path/<name>.npy`` in float32.  Outputs larger
+    than DUMP_LIMIT_BYTES in all are written as a fixed, seeded sample of each flattened array (the same elements every run)."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() * 4 for t in arrays.values())
+    for name, t in arrays.items():
+        a = t.numpy().astype(np.float32, copy=False)
+        if total > DUMP_LIMIT_BYTES:
+            idx = np.random.RandomState(0).choice(a.size, size=max(1, a.size * DUMP_LIMIT_BYTES // total), replace=False)
+            a = a.reshape(-1)[np.sort(idx)]
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 def c5_global_leg(head, C, dev, rank, world, ksteps, rotate=3):
     """One GLOBAL ragged batch of 64 samples per step (views ~ U{2..10}, seed 5), the same on every rank, cut into contiguous
     sample ranges by dist.shard_by_views; each rank runs its shard, the step time is the slowest rank's.  Then the claim the
@@ -504,12 +522,21 @@ def main():
                     help="skip the short legs for the other BASELINE per-GPU loads (c3 medium_MANO, c4 large x 10 views x 16, "
                          "c5 ragged 2-10 views x 64)")
     ap.add_argument("--headline-only", action="store_true",
-                    help="only the headline leg (no opt-in / A-B / extra-config / pyramid / E2E / input / CPU / eager legs): the command "
-                         "tools/collect_profiles.sh profiles, so that the per-kernel averages of rocprofv3 --stats are the headline's")
+                    help="with --full: the headline leg and its roofline events leg only (no opt-in / A-B / extra-config / pyramid / "
+                         "E2E / input / CPU / eager legs)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline: roofline events leg, scaling diagnostics, opt-in precision and A/B legs, "
+                         "extra configs, pyramid / E2E / input scopes, CPU and eager baselines, the c5 global batch.  Off: the run "
+                         "sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32), rank 0")
     ap.add_argument("--rotate", type=int, default=8, help="resident input batches cycled through the steps (>= 8 x 42 MB of "
                     "features outruns the 256 MB Infinity Cache, so the sampling front end is timed cold)")
     args = ap.parse_args()
-    if args.headline_only:
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    legs = args.full and not args.headline_only     # the measurements beside the headline (--full)
+    if not legs:
         args.no_e2e = args.no_extra_configs = True
         args.cpu_samples = 0
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -592,19 +619,23 @@ def main():
         step_ms = sorted(marks[i].elapsed_time(marks[i + 1]) for i in range(args.steps))
         graph_stats = eng.graph_stats()
         mpvpe_timed = meter.result() * 1e3
-        # separate short leg for the roofline: the same steps with the library's HIP events around the dominant kernel and the
-        # sampling stage (plain launches, ~130 event records per step -- which is why it is not the timed region)
-        ev_steps = max(2, min(args.steps, 6))
-        eng.profile_enable(8 * ev_steps)
-        for _ in range(ev_steps):
-            step()
-        torch.cuda.synchronize()
+        if args.dump_outputs and rank == 0:
+            # copied now: the returned tensors live in the engine's buffers, which later forwards overwrite
+            dump_outputs(args.dump_outputs, {k: v.detach().float().cpu() for k, v in preds.items()})
+        if args.full:
+            # separate short leg for the roofline: the same steps with the library's HIP events around the dominant kernel and
+            # the sampling stage (plain launches, ~130 event records per step -- which is why it is not the timed region)
+            ev_steps = max(2, min(args.steps, 6))
+            eng.profile_enable(8 * ev_steps)
+            for _ in range(ev_steps):
+                step()
+            torch.cuda.synchronize()
     dt_rank = dt
     tmax = torch.tensor([dt], dtype=torch.float64, device=dev)
     pdist.all_reduce_max_(tmax)
     dt = float(tmax.item())
     scale_diag = None
-    if grouped:
+    if grouped and args.full:
         # what a reader of the scaling curve needs beside `value`: every rank's own step time (min / max / spread) and the
         # latency of the path's only collective (the 16-byte all-reduce of the metric sums), measured alone
         per = torch.zeros(world, dtype=torch.float64, device=dev)
@@ -624,10 +655,12 @@ def main():
                       "ms_per_step_max": float(per.max()), "allreduce_16B_latency_us": ar_us,
                       "note": "per-rank wall time of the timed region / steps (rank-local clocks, same barrier-bracketed region); "
                               "the all-reduce is timed alone, back to back, 50 calls"}
-    n_fe, fe_ms = eng.profile_read_stage(2)            # the sampling front end (input_proj .. merge finalize), per forward
-    n_anch, anch_ms = eng.profile_read_anchored()      # block 0's table form (one C x C GEMM per neighbour column)
-    n_launch, va_ms = eng.profile_read()               # the full fused kernel (blocks 1, 2)
-    eng.profile_enable(0)
+    n_fe = n_anch = n_launch = 0
+    if args.full:
+        n_fe, fe_ms = eng.profile_read_stage(2)            # the sampling front end (input_proj .. merge finalize), per forward
+        n_anch, anch_ms = eng.profile_read_anchored()      # block 0's table form (one C x C GEMM per neighbour column)
+        n_launch, va_ms = eng.profile_read()               # the full fused kernel (blocks 1, 2)
+        eng.profile_enable(0)
 
     total_samples = args.batch * world * args.steps
     value = total_samples / dt
@@ -723,7 +756,7 @@ def main():
             res["roofline"].update(kernel="vecattn_split_kernel", peak=F16_MFMA_PEAK_TFLOPS / 3.0,
                                    frac=res["roofline"]["achieved"] / (F16_MFMA_PEAK_TFLOPS / 3.0), traffic=None,
                                    note="peak = dense f16 MFMA peak / 3 (three MFMAs per fp32-equivalent product)")
-    elif C >= 128 and not parametric and world == 1 and not args.headline_only:
+    elif C >= 128 and not parametric and world == 1 and legs:
         # OPT-IN split-precision leg, reported beside the headline (never as `value`): same step with
         # poem_set_precision(SPLIT_F16X3); distance of its vertices from the fp32 path's on the same batch.
         try:
@@ -766,7 +799,7 @@ def main():
                                                 "everything else fp32; the headline `value` is the exact-fp32 default"}
         except Exception as e:
             res["split_f16x3_scope"] = {"error": repr(e)[:200]}
-    if world == 1 and args.precision == "fp32" and args.anchor_tables and not args.headline_only:
+    if world == 1 and args.precision == "fp32" and args.anchor_tables and legs:
         # the same step with block 0's positional products evaluated per sample, term by term as the reference does
         # (poem_set_anchor_tables(0)): what the anchor tables buy, and how far the two forms are apart on this batch
         try:
@@ -891,7 +924,7 @@ def main():
         except Exception as e:   # informational: never fail the bench line on it
             res["predicted_c5_strong_scaling"] = {"error": repr(e)[:200]}
         torch.cuda.empty_cache()
-    if world == 1 and not args.views_range and not parametric and not args.headline_only:
+    if world == 1 and not args.views_range and not parametric and legs:
         # one stage earlier (SURVEY 8f rows N1 + N2): backbone pyramid -> feat_decode / heatmap_stage -> DLT -> head.  The
         # HRNet backbone itself is out of scope; its output pyramid is synthetic.  Reported beside the headline, never as it.
         try:
@@ -1067,7 +1100,7 @@ def main():
             res["speedup_vs_eager"] = value / res["eager_baseline"]["value"]
         except Exception as e:   # the eager leg is informational: never fail the bench line on it
             res["eager_baseline"] = {"error": repr(e)[:200]}
-    if grouped and args.precision == "fp32" and not args.headline_only and not args.views_range and not parametric:
+    if grouped and args.precision == "fp32" and legs and not args.views_range and not parametric:
         # BASELINE configs[4] as ONE global batch: 64 samples with 2..10 views each (seed 5), split over the ranks by
         # dist.shard_by_views (contiguous sample ranges balanced by their view counts) -- strong scaling of that batch, next
         # to the weak-scaling headline above.  No data-path collective: each rank runs its shard, the time is the slowest rank's.

@@ -159,7 +159,7 @@ def test_bench_line_over_a_one_rank_rccl_group():
     max-over-ranks of the time, scaling_diagnostics with the all-reduce latency, the c5 global batch with the shard join --
     execute over RCCL."""
     out = _launch(1, [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "8", "--rotate", "2",
-                      "--cpu-samples", "0", "--no-e2e", "--no-extra-configs"], _env(POEM_DIST_FORCE_INIT="1"), 1200)
+                      "--cpu-samples", "0", "--no-e2e", "--no-extra-configs", "--full"], _env(POEM_DIST_FORCE_INIT="1"), 1200)
     res = _bench_line(out)
     assert res["n_gpus"] == 1 and res["config"]["process_group"] == "nccl world_size=1" and res["value"] > 0
     sd = res["scaling_diagnostics"]
@@ -181,7 +181,7 @@ def test_bench_gpus_8_rehearsal_shards_are_bit_equal_to_one_process():
         env = _env(POEM_SINGLE_DEVICE="1")
     env["OMP_NUM_THREADS"] = "4"
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "2", "--warmup", "1", "--batch", "2",
-                          "--rotate", "2", "--cpu-samples", "0", "--no-e2e", "--no-extra-configs"],
+                          "--rotate", "2", "--cpu-samples", "0", "--no-e2e", "--no-extra-configs", "--full"],
                          capture_output=True, text=True, env=env, timeout=1800)
     res = _bench_line(out)
     assert res["n_gpus"] == 8 and res["config"]["ranks_joined"] == 8 and "world_size=8" in res["config"]["process_group"]

@@ -1541,6 +1541,37 @@ def test_bench_gpus_2_launches_two_ranks_or_refuses():
     assert res["value"] > 0 and res["scaling"] == "weak"
 
 
+def test_bench_plain_line_and_dumped_outputs(tmp_path):
+    """A plain bench.py run (no --full) prints the headline line with its own `steps` and `ms_per_step` and none of the
+    --full legs; --dump-outputs writes the last timed step's vertices, which a fresh head on the same seeded batch reproduces."""
+    import importlib.util
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    steps, warmup, rotate, batch = 3, 2, 2, 4
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
+                          "--batch", str(batch), "--rotate", str(rotate), "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=600)
+    assert out.returncode == 0, out.stderr[-3000:]
+    res = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert res["steps"] == steps and res["ms_per_step"] > 0 and res["value"] > 0
+    for k in ("metric", "unit", "higher_is_better", "dtype"):
+        assert k in res, k
+    for k in ("roofline", "cpu_baseline", "extra_configs", "pyramid_scope", "split_f16x3_scope", "per_sample_block0_scope"):
+        assert k not in res, k
+    got = np.load(tmp_path / "dump" / "all_coords_preds.npy")
+    assert got.dtype == np.float32 and got.shape == (3, batch, 799, 3)
+    spec = importlib.util.spec_from_file_location("bench", os.path.join(root, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    head, batches, _ = bench.make_leg(pk.weights.MODEL_EMBED["medium"], [8] * batch, False, torch.device(DEV), 0, rotate)
+    with torch.no_grad():
+        ref = head(*batches[(warmup + steps - 1) % rotate][:3])["all_coords_preds"].cpu().numpy()
+    assert np.abs(got - ref).max() < 1e-6, np.abs(got - ref).max()
+
+
 def test_eval_single_script_runs_the_path(tmp_path):
     """The eval_single.py counterpart end to end on the GPU (tiny synthetic epoch), cfg written back as upstream does."""
     import json

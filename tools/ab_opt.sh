@@ -1,7 +1,7 @@
 #!/bin/bash
 # A/B of poem_set_option switches on ONE box, interleaved: tools/ab_opt.sh "name=value[,name=value]" ...  ("-" = defaults)
 REPS=${REPS:-3}
-EXTRA=${EXTRA:---headline-only --steps 20 --warmup 5}
+EXTRA=${EXTRA:---full --headline-only --steps 20 --warmup 5}
 for i in $(seq $REPS); do
   for SPEC in "$@"; do
     OPTS=""

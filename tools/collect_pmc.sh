@@ -10,7 +10,7 @@ OUT=gpurun_out/prof_$TAG
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p $OUT
 echo "$ARGS" > $OUT/args.txt
-run() { rocprofv3 --kernel-trace --pmc $2 --output-format csv -d $OUT/$1 -o pmc -- python bench.py --steps 1 --warmup 1 --headline-only --cpu-samples 0 --option graphs=0 $ARGS > /dev/null 2> $OUT/$1.err; }
+run() { rocprofv3 --kernel-trace --pmc $2 --output-format csv -d $OUT/$1 -o pmc -- python bench.py --full --steps 1 --warmup 1 --headline-only --cpu-samples 0 --option graphs=0 $ARGS > /dev/null 2> $OUT/$1.err; }
 run pmc_fetch FETCH_SIZE
 run pmc_write WRITE_SIZE
 run pmc_mfma "SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE"

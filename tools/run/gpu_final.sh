@@ -6,9 +6,9 @@ OUT=gpurun_out/final_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 T0=$(date +%s)
-python bench.py > $OUT/bench_unprofiled.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench_unprofiled.json 2> $OUT/bench.err
 echo "bench wall $(( $(date +%s) - T0 )) s" | tee $OUT/wall.txt
-rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python bench.py --headline-only > /dev/null 2> $OUT/trace.err
+rocprofv3 --kernel-trace --output-format csv -d $OUT/trace -o t -- python bench.py --full --headline-only > /dev/null 2> $OUT/trace.err
 T=$(find $OUT/trace -name "*kernel_trace.csv" | head -1)
 python tools/step_timeline.py $T 9 > $OUT/timeline_B32.txt 2>> $OUT/trace.err
 rm -rf $OUT/trace
