@@ -80,10 +80,11 @@ typedef struct poem_config {
   int32_t nquery;      /* Q: 799 */
   int32_t heads;       /* NUM_ATTENTION_HEADS (4) */
   int32_t nblocks;     /* N_BLOCKS (3) */
-  int32_t knn;         /* N_NEIGHBOR (ptEmb_transformer.py:30), 1..32; N_NEIGHBOR_QUERY (:31) is the same unless
-                          poem_set_option(h, "knn_query", k) says otherwise.  The release configs set 32 for both; counts below 32
-                          run the masked vector attention (the search's first k of its 32 nearest).  Block 0 takes the 32 fixed
-                          anchors whatever the keys say (assets/anchor.npy, point_transformers.py:10-32). */
+  int32_t knn;         /* N_NEIGHBOR (ptEmb_transformer.py:30), 1..64 and <= nsample, nquery; N_NEIGHBOR_QUERY (:31) is the same
+                          unless poem_set_option(h, "knn_query", k) says otherwise.  The release configs set 32 for both; counts
+                          below 32 run the masked vector attention (the search's first k of its 32 nearest); a count above 32
+                          switches both neighbour buffers to rows of 64 and the K <= 64 search / two-tile attention.  Block 0
+                          takes the 32 fixed anchors whatever the keys say (assets/anchor.npy, point_transformers.py:10-32). */
   int32_t parametric;  /* TRANSFORMER.PARAMETRIC_OUTPUT */
   int32_t feat_h, feat_w; /* backbone feature map (16x16) */
   int32_t max_views;   /* largest views-per-sample the positional table is folded for */
@@ -185,7 +186,8 @@ int poem_set_chains(poem_handle_t h, int enable);
  * kernels, 1 = 32 rows, 2 = 64 rows (csrc/chain.hip), 3 = 16-row units on v_mfma_f32_16x16x4_f32 (csrc/chain16.hip) -- any
  * choice gives the same bits; "knn_fma" (default 0): neighbour distances rounded as pytorch3d's CUDA kernel (poem_knn_ex below)
  * -- the one switch that is NOT round-off neutral by design.
- * "knn_query" (round 6; default 0 = poem_config_t.knn): N_NEIGHBOR_QUERY, 1..32 -- part of the model's configuration, not an A/B switch.
+ * "knn_query" (round 6; default 0 = poem_config_t.knn): N_NEIGHBOR_QUERY, 0..64 and <= nquery -- part of the model's configuration,
+ * not an A/B switch; poem_workspace_bytes follows it (a count above 32 widens the neighbour buffers).
  * Round 4, all bit-identical: "gemm_xcd_map" (default 1; process-wide): panel GEMM blocks of one XCD own a row range and all its
  * column panels (csrc/gemm.hip); "f1_split" (default 1): the basis-point GEMM of blocks >= 1 as a 4C- and a 2C-column launch;
  * "gemm_kslab" (default 1; process-wide): K >= 512 Linears on the K-slab kernel; "bps_defer" (default 0): 1 / 2 / 3 = the
@@ -484,6 +486,16 @@ int poem_vector_attention(const float* query_xyz, const float* src_xyz, const fl
                           const float* wd1, const float* bd1, const void* wd2_packed, const float* bd2,
                           const void* wg1_packed, const float* bg1, const void* wg2_packed, const float* bg2,
                           float* out, int batch, int nq, int embed, void* stream);
+/* Any neighbour count k in 1..64 (N_NEIGHBOR / N_NEIGHBOR_QUERY above 32).  poem_knn_k: the k nearest of poem_knn_ex's order,
+ * idx (B,Q,ld) int32 with ld >= k (columns k..ld-1 untouched), 1 <= k <= nsrc.  poem_vector_attention_k: poem_vector_attention
+ * over the first k columns of idx (B,Q,ld), neighbour coordinates src_xyz[b, idx] (no anchors), key rows `key` (B,NS,C);
+ * softmax over the k neighbours, taken as 32-column tiles folded by an online softmax. */
+int poem_knn_k(const float* query_xyz, const float* src_xyz, int32_t* idx, int batch, int nq, int nsrc, int k, int ld,
+               int fma_contract, void* stream);
+int poem_vector_attention_k(const float* query_xyz, const float* src_xyz, const int32_t* idx, int k, int ld, const float* q,
+                            const float* key, const float* v, int nsrc, const float* wd1, const float* bd1,
+                            const void* wd2_packed, const float* bd2, const void* wg1_packed, const float* bg1,
+                            const void* wg2_packed, const float* bg2, float* out, int batch, int nq, int embed, void* stream);
 /* xyz_out = xyz_in + r . W^T + b   (W (3,C) raw) */
 int poem_reg_update(const float* r, const float* w, const float* b, const float* xyz_in, float* xyz_out, int rows,
                     int embed, void* stream);

@@ -176,8 +176,13 @@ struct DecoderRun {
       if (!recorded) HIPCHK(hipEventRecord(h->ev_xyz[i], s));            // xyz_i is final here
       HIPCHK(hipStreamWaitEvent(sk, h->ev_xyz[i], 0));
     }
-    HIPCHK(poem_launch_knn(p.xyz[i], pt_xyz, p.idx_cross[i], B, Q, S, h->knn_fma, sk));
-    HIPCHK(poem_launch_knn(p.xyz[i], p.xyz[i], p.idx_self[i], B, Q, Q, h->knn_fma, sk));
+    if (p.idx_ld == 32) {
+      HIPCHK(poem_launch_knn(p.xyz[i], pt_xyz, p.idx_cross[i], B, Q, S, h->knn_fma, sk));
+      HIPCHK(poem_launch_knn(p.xyz[i], p.xyz[i], p.idx_self[i], B, Q, Q, h->knn_fma, sk));
+    } else {     // a count above 32: N_NEIGHBOR / N_NEIGHBOR_QUERY nearest at row stride 64
+      HIPCHK(poem_launch_knn_k(p.xyz[i], pt_xyz, p.idx_cross[i], B, Q, S, c.knn, p.idx_ld, h->knn_fma, sk));
+      HIPCHK(poem_launch_knn_k(p.xyz[i], p.xyz[i], p.idx_self[i], B, Q, Q, h->knn_query ? h->knn_query : c.knn, p.idx_ld, h->knn_fma, sk));
+    }
     if (ov) HIPCHK(hipEventRecord(h->ev_knn[i], sk));
     knn_issued[i] = true;
     return POEM_OK;
@@ -337,6 +342,10 @@ struct DecoderRun {
       HIPCHK(poem_launch_vector_attention_anchored(p.ident, p.y3, p.anch_kv[0], p.anch_kv[0] + C, 32, h->P(vsb + 10), p.tab_g[0],
                                                    p.tab_p[0], p.rs, B, Q, C, 3 * C, 2 * C, 2 * C, s));
       }
+    } else if (!shared && p.idx_ld != 32) {             // N_NEIGHBOR_QUERY on neighbour rows of stride 64 (vecattn.hip MODE 4)
+      HIPCHK(poem_launch_vector_attention_k(xyz, xyz, idx_s, kq, p.idx_ld, p.y3, p.y3 + C, p.y3 + 2 * C, Q, h->R(vsb + 4), h->R(vsb + 5),
+                                            h->P(vsb + 6), h->R(vsb + 7), h->fused[i].w[5], h->R(vsb + 9), h->P(vsb + 10), h->R(vsb + 11),
+                                            p.rs, B, Q, C, 3 * C, 3 * C, 3 * C, 1, s));
     } else {
       poem_vecattn_one_query_blocks(h->va_p1);           // (thread-local launcher switches: this handle's values for this launch only)
       poem_vecattn_valid_neighbours(kq);
@@ -383,6 +392,10 @@ struct DecoderRun {
       if (ov) HIPCHK(hipStreamWaitEvent(s, h->ev_xyz[0], 0));      // the anchor rows of (kc | vc), basis_point_side(0)
       HIPCHK(poem_launch_vector_attention_anchored(p.ident, p.qc, p.anch_kv[1], p.anch_kv[1] + C, 32, h->P(vcb + 10), p.tab_g[1],
                                                    p.tab_p[1], p.rc, B, Q, C, C, 2 * C, 2 * C, s));
+    } else if (!shared && p.idx_ld != 32) {             // N_NEIGHBOR on neighbour rows of stride 64 (vecattn.hip MODE 4)
+      HIPCHK(poem_launch_vector_attention_k(xyz, pt_xyz, idx_c, kc, p.idx_ld, p.qc, p.y1[i] + 4 * (size_t)BS * C, p.y1[i] + 5 * (size_t)BS * C,
+                                            S, h->R(vcb + 4), h->R(vcb + 5), h->P(vcb + 6), h->R(vcb + 7), h->fused[i].w[6], h->R(vcb + 9),
+                                            h->P(vcb + 10), h->R(vcb + 11), p.rc, B, Q, C, C, C, C, 1, s));
     } else {
       poem_vecattn_one_query_blocks(h->va_p1);
       poem_vecattn_valid_neighbours(kc);

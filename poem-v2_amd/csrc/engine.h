@@ -175,7 +175,9 @@ struct poem_handle_s {
   const float* mano_table = nullptr;
   int mano_center = 9;
   int knn_query = 0;         // N_NEIGHBOR_QUERY when it differs from cfg.knn (= N_NEIGHBOR); 0: the same.  Both 1..32: counts below 32 mask
-                             // the vector attention's last columns (vecattn.hip MODE 3); block 0 takes the 32 anchors either way (Q2)
+                             // the vector attention's last columns (vecattn.hip MODE 3); either above 32 (up to 64): the K <= 64
+                             // search and vecattn.hip MODE 4 on neighbour rows of stride 64 (neighbour_ld); block 0 takes the 32
+                             // anchors either way (Q2)
   int knn_fma = 0;           // neighbour distances with the fma contraction of pytorch3d's CUDA kernel (knn.hip); default: the CPU path's rounding
   int chain_tile = 0;        // chain row-tile height: 0 = per launch (chain.hip chain_tile_p), 1 = 32 rows, 2 = 64 rows (A/B)
   // The block-0 anchor tables are functions of the handle's constants only (template, anchors, weights): like the folded
@@ -255,10 +257,15 @@ struct Plan {
   float *canon_xyz, *tab_g[2], *tab_p[2];   // block-0 anchor tables (self, cross) of the head path
   float *anch_x[2], *anch_kv[2], *qeqp0;    // block 0: anchor rows of the key/value sources, their (k | v) rows; F2 on Q rows
   int32_t* ident;
+  int idx_ld;      // row stride of idx_self / idx_cross: 32, or 64 when a neighbour count is above 32 (neighbour_ld)
   size_t bytes;
 };
 
-Plan make_plan(const poem_config_t& c, int B, int BN, void* base);
+// Row stride of the neighbour index buffers for N_NEIGHBOR = c.knn and N_NEIGHBOR_QUERY = knn_query (0: the same): 32 while
+// both are <= 32 (every 32-neighbour launch, tap and workspace size as before), else 64.
+inline int neighbour_ld(const poem_config_t& c, int knn_query) { return (c.knn > 32 || knn_query > 32) ? 64 : 32; }
+
+Plan make_plan(const poem_config_t& c, int B, int BN, void* base, int idx_ld);
 void register_taps(poem_handle_t h, const Plan& p, int B, int BN, bool sampling);
 
 // handle.cpp: a retired exec is parked, not destroyed (runtime bug, see there), and offered to the next capture of the same shape

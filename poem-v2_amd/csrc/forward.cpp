@@ -49,7 +49,7 @@ struct HeadRun {
   // caller's workspace holds that plan -- one graph per batch size, whatever the view layout -- else this batch's own total.
   HeadRun(poem_handle_t h_, const float* feat, const float* intr, const float* extr, const int32_t* offs, int batch, int plan_views_,
           const float* ref_joints, int w, int hgt, void* workspace, hipStream_t s_)
-      : h(h_), c(h_->cfg), p(make_plan(h_->cfg, batch, plan_views_, workspace)), plan_views(plan_views_), mlvl_feat(feat), cam_intr(intr), cam_extr(extr),
+      : h(h_), c(h_->cfg), p(make_plan(h_->cfg, batch, plan_views_, workspace, neighbour_ld(h_->cfg, h_->knn_query))), plan_views(plan_views_), mlvl_feat(feat), cam_intr(intr), cam_extr(extr),
         reference_joints(ref_joints), offs_host(offs), B(batch), BN(offs[batch]), C(c.embed), S(c.nsample), Q(c.nquery),
         HW(c.feat_h * c.feat_w), BS(batch * c.nsample), img_w(w), img_h(hgt), s(s_) {}
 
@@ -333,7 +333,7 @@ int poem_head_forward(poem_handle_t h, const float* mlvl_feat, const float* cam_
   const int total_views = view_offsets_host[batch];
   const long cap_views = (long)batch * c.max_views;
   int plan_views = total_views;
-  if (cap_views > total_views && cap_views < (1l << 30) && workspace_bytes >= make_plan(c, batch, (int)cap_views, nullptr).bytes)
+  if (cap_views > total_views && cap_views < (1l << 30) && workspace_bytes >= make_plan(c, batch, (int)cap_views, nullptr, neighbour_ld(c, h->knn_query)).bytes)
     plan_views = (int)cap_views;
   HeadRun run(h, mlvl_feat, cam_intr, cam_extr, view_offsets_host, batch, plan_views, reference_joints, img_w, img_h, workspace,
               (hipStream_t)stream);
@@ -365,7 +365,7 @@ int poem_decoder_forward(poem_handle_t h, const float* query_xyz, const float* q
   const poem_config_t& c = h->cfg;
   if (c.nblocks > 8) return POEM_E_UNSUPPORTED;
   if (c.parametric && (!pose_aa || !betas)) return POEM_E_ARG;
-  Plan p = make_plan(c, batch, batch, workspace);
+  Plan p = make_plan(c, batch, batch, workspace, neighbour_ld(c, h->knn_query));
   if (workspace_bytes < p.bytes) return POEM_E_WORKSPACE;
   hipStream_t s = (hipStream_t)stream;
   const size_t n = (size_t)batch * c.nquery * 3;

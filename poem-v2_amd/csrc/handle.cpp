@@ -222,12 +222,14 @@ int check_config(const poem_config_t* c) {
   if (!c) return POEM_E_ARG;
   const int C = c->embed;
   if (C < 32 || C > 1024 || (C & (C - 1))) return POEM_E_UNSUPPORTED;       // 32,64,...,1024
-  if (c->knn < 1 || c->knn > 32) return POEM_E_UNSUPPORTED;       // the attention tile holds 32 neighbour columns (vecattn.hip)
+  // N_NEIGHBOR: 1..32 in one 32-column attention tile (MODE 0 / 3), 33..64 as two tiles one after the other (vecattn.hip MODE 4)
+  if (c->knn < 1 || c->knn > 64) return POEM_E_UNSUPPORTED;
   if (c->in_channels % 8 || c->nsample % 32 || c->nsample % C) return POEM_E_UNSUPPORTED;
   if (c->heads <= 0 || C % c->heads) return POEM_E_UNSUPPORTED;
   const int dh = C / c->heads;
   if (!(dh == 8 || dh == 16 || dh == 32 || dh == 64 || dh == 128 || dh == 256)) return POEM_E_UNSUPPORTED;
   if (c->nsample > 4096 || c->nquery > 4096 || c->nquery < 33) return POEM_E_UNSUPPORTED;
+  if (c->knn > c->nsample || c->knn > c->nquery) return POEM_E_UNSUPPORTED;      // K distinct neighbours among the basis points / queries
   if ((c->feat_h * c->feat_w) % 32) return POEM_E_UNSUPPORTED;
   if (c->max_views < 1 || c->max_views > 64 || c->nblocks < 1) return POEM_E_ARG;
   if (c->petr_embedding) {
@@ -540,7 +542,7 @@ int poem_set_option(poem_handle_t h, const char* name, int value) {
   else if (k == "tables_cached") h->tables_cached = value != 0;
   else if (k == "knn_fma") h->knn_fma = value != 0;
   else if (k == "knn_query") {
-    if (value < 0 || value > 32) return POEM_E_ARG;
+    if (value < 0 || value > 64 || value > h->cfg.nquery) return POEM_E_ARG;      // (the workspace grows with it: neighbour_ld)
     if (h->precision != POEM_PRECISION_FP32 && value != 0 && value != 32) return POEM_E_UNSUPPORTED;
     h->knn_query = value;
   }

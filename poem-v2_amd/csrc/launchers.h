@@ -67,11 +67,18 @@ hipError_t poem_launch_chain(const ChainArgs* a, int C, hipStream_t s);
 hipError_t poem_launch_native16(const void* packed, void* native, size_t bytes, hipStream_t s);
 int poem_chain16_wants_native(int C);
 hipError_t poem_launch_knn(const float* qxyz, const float* sxyz, int* idx, int B, int NQ, int NS, int fma, hipStream_t s);
+hipError_t poem_launch_knn_k(const float* qxyz, const float* sxyz, int* idx, int B, int NQ, int NS, int K, int ld, int fma,
+                             hipStream_t s);
 hipError_t poem_launch_vector_attention(const float* query_xyz, const float* src_xyz, const float* anchor_xyz,
                                         const int* idx, int shared_idx, const float* q, const float* k, const float* v,
                                         int nsrc, const float* wd1, const float* bd1, const void* wd2, const float* bd2,
                                         const void* wg1, const float* bg1, const void* wg2, const float* bg2, float* out,
                                         int B, int Q, int C, int ldq, int ldk, int ldv, int composed, hipStream_t s);
+hipError_t poem_launch_vector_attention_k(const float* query_xyz, const float* src_xyz, const int* idx, int K, int ld,
+                                          const float* q, const float* k, const float* v, int nsrc, const float* wd1,
+                                          const float* bd1, const void* wd2, const float* bd2, const void* wg1, const float* bg1,
+                                          const void* wg2, const float* bg2, float* out, int B, int Q, int C, int ldq, int ldk,
+                                          int ldv, int composed, hipStream_t s);
 size_t poem_vector_attention_table_floats(int Q, int C);
 hipError_t poem_launch_vector_attention_tables(const float* query_xyz, const float* anchor_xyz, const int* idx,
                                                const float* wd1, const float* bd1, const void* wd2, const float* bd2,

@@ -186,6 +186,27 @@ int poem_knn_ex(const float* query_xyz, const float* src_xyz, int32_t* idx, int 
   return POEM_OK;
 }
 
+int poem_knn_k(const float* query_xyz, const float* src_xyz, int32_t* idx, int batch, int nq, int nsrc, int k, int ld,
+               int fma_contract, void* stream) {
+  if (!query_xyz || !src_xyz || !idx || batch <= 0 || nq <= 0 || nsrc < 1 || nsrc > 4096 || k < 1 || k > 64 || k > nsrc ||
+      ld < k || (fma_contract & ~1))
+    return POEM_E_ARG;
+  HIPCHK(poem_launch_knn_k(query_xyz, src_xyz, idx, batch, nq, nsrc, k, ld, fma_contract, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_vector_attention_k(const float* query_xyz, const float* src_xyz, const int32_t* idx, int k, int ld, const float* q,
+                            const float* key, const float* v, int nsrc, const float* wd1, const float* bd1,
+                            const void* wd2_packed, const float* bd2, const void* wg1_packed, const float* bg1,
+                            const void* wg2_packed, const float* bg2, float* out, int batch, int nq, int embed, void* stream) {
+  if (!query_xyz || !src_xyz || !idx || !q || !key || !v || !wd1 || !bd1 || !wd2_packed || !bd2 || !wg1_packed || !bg1 ||
+      !wg2_packed || !bg2 || !out || batch <= 0 || nq <= 0 || nsrc <= 0 || k < 1 || k > 64 || ld < k)
+    return POEM_E_ARG;
+  HIPCHK(poem_launch_vector_attention_k(query_xyz, src_xyz, idx, k, ld, q, key, v, nsrc, wd1, bd1, wd2_packed, bd2, wg1_packed, bg1,
+                                        wg2_packed, bg2, out, batch, nq, embed, embed, embed, embed, 0, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 int poem_vector_attention(const float* query_xyz, const float* src_xyz, const float* anchor_xyz, const int32_t* idx,
                           int shared_idx, const float* q, const float* k, const float* v, int nsrc, const float* wd1,
                           const float* bd1, const void* wd2_packed, const float* bd2, const void* wg1_packed,

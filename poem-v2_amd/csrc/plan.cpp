@@ -2,8 +2,9 @@
 // debug taps over it.
 #include "engine.h"
 
-Plan make_plan(const poem_config_t& c, int B, int BN, void* base) {
+Plan make_plan(const poem_config_t& c, int B, int BN, void* base, int idx_ld) {
   Plan p{};
+  p.idx_ld = idx_ld;
   Arena a(base);
   const size_t C = c.embed, S = c.nsample, Q = c.nquery, HW = (size_t)c.feat_h * c.feat_w;
   const size_t BS = (size_t)B * S, BQ = (size_t)B * Q, VS = (size_t)BN * S;
@@ -51,8 +52,8 @@ Plan make_plan(const poem_config_t& c, int B, int BN, void* base) {
     p.f_self[i] = a.take<float>(BQ * C);
     p.f_cross[i] = a.take<float>(BQ * C);
     p.feats[i] = a.take<float>(BQ * C);
-    p.idx_self[i] = a.take<int32_t>(BQ * 32);
-    p.idx_cross[i] = a.take<int32_t>(BQ * 32);
+    p.idx_self[i] = a.take<int32_t>(BQ * idx_ld);
+    p.idx_cross[i] = a.take<int32_t>(BQ * idx_ld);
     p.y1[i] = a.take<float>(BS * C * 6);
   }
   p.q3t = a.take<float>((size_t)B * C);
@@ -104,8 +105,8 @@ void register_taps(poem_handle_t h, const Plan& p, int B, int BN, bool sampling)
     put(pre + "feats", p.feats[i], BQ * C);
     put(pre + "xyz", p.xyz[i + 1], BQ * 3);
     if (i > 0) {
-      put(pre + "idx_self", p.idx_self[i], BQ * 32);
-      put(pre + "idx_cross", p.idx_cross[i], BQ * 32);
+      put(pre + "idx_self", p.idx_self[i], BQ * p.idx_ld);
+      put(pre + "idx_cross", p.idx_cross[i], BQ * p.idx_ld);
     }
   }
 }
@@ -115,6 +116,6 @@ extern "C" {
 // ---- whole path: workspace -------------------------------------------------------------------------------------------
 size_t poem_workspace_bytes(poem_handle_t h, int batch, int total_views) {
   if (!h || batch <= 0 || total_views < batch || h->cfg.nblocks > 8) return 0;
-  return make_plan(h->cfg, batch, total_views, nullptr).bytes;
+  return make_plan(h->cfg, batch, total_views, nullptr, neighbour_ld(h->cfg, h->knn_query)).bytes;
 }
 }  // extern "C"

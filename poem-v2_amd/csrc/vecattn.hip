@@ -50,7 +50,9 @@ struct VecAttnArgs {
   int composed;             // 1: q, k are W_g1 q + (W_g1 b_d2 + b_g1) and W_g1 k, `wg1` is W_g1 W_d2 (see vecattn_kernel)
   float4* tab_g;            // MODE 1 writes / MODE 2 reads: (W_g1 W_d2) h_ij per (query, anchor), C/D fragment images
   float4* tab_p;            // MODE 1 writes / MODE 2 reads: pos_ij = W_d2 h_ij + b_d2, transposed (lane = channel) images
-  int kvalid;               // MODE 3: the first `kvalid` of the 32 neighbour columns count (N_NEIGHBOR / N_NEIGHBOR_QUERY < 32)
+  int kvalid;               // MODE 3: the first `kvalid` of the 32 neighbour columns count (N_NEIGHBOR / N_NEIGHBOR_QUERY < 32);
+                            // MODE 4: the neighbour count K, 1..64
+  int ldidx;                // MODE 4: row stride of idx (>= kvalid)
 };
 
 // arrival parity per CU (key: XCC id, HW_ID[15:8]); atomicInc wraps 0 -> 1 -> 0, so the table resets itself when
@@ -158,10 +160,17 @@ __device__ __forceinline__ void chain_gemm(const float4* __restrict__ Wp, const 
 //           upstream; every release config sets 32): the search returns its 32 nearest in ascending order, the tile keeps its 32
 //           columns, and the softmax takes the columns from `kvalid` on as -inf -- weight exactly 0 in the sum and in the weighted
 //           sum.  The 32-neighbour kernels are untouched by it.
+//   MODE 4  any K in 1..64 (N_NEIGHBOR / N_NEIGHBOR_QUERY above 32), plain or composed: K neighbour ids per query at row
+//           stride `ldidx`, taken as ceil(K / 32) chunks of 32 columns one after the other inside the item -- the block's
+//           LDS and tile are MODE 0's, so P = 1 at C = 512 / 1024 works unchanged.  Each chunk runs stage 0 and the three GEMMs
+//           as MODE 0 does; its softmax epilogue (lane = channel) folds the chunk into a running (max, sum, weighted sum) per
+//           output channel, and the last chunk writes.  The last chunk's columns from K on read neighbour K - 1 (in bounds) and
+//           are -inf in the softmax: weight exactly 0.
 template <int C, int P, int NW, int MINW, bool COMP, int MODE = 0>
 __global__ __launch_bounds__(NW * 64, MINW) void vecattn_kernel(VecAttnArgs A) {
-  static_assert(MODE == 0 || COMP, "table modes exist for the composed form only");
+  static_assert(MODE == 0 || MODE == 4 || COMP, "table modes exist for the composed form only");
   constexpr bool MASK = MODE == 3;
+  constexpr bool WIDE = MODE == 4;
   constexpr int NTILE = C / 32;
   constexpr int TPW = C / 32 / NW;
   constexpr int XS = 32 * P;
@@ -197,7 +206,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void vecattn_kernel(VecAttnArgs A) {
 
   for (int item = blockIdx.x; item < total; item += gridDim.x) {
   int b = item / groups, ig = item % groups;
-  if ((MODE == 0 || MODE == 3) && POEM_VA_XCD_SAMPLES && gridDim.x == (unsigned)total && (total & 7) == 0) {
+  if ((MODE == 0 || MODE == 3 || WIDE) && POEM_VA_XCD_SAMPLES && gridDim.x == (unsigned)total && (total & 7) == 0) {
     // block ids go round-robin over the 8 XCDs: XCD x takes the x-th eighth of the (sample, query group) list, i.e. whole
     // samples -- a sample's key / value rows (8 MB at S = 4096, C = 256) are then gathered through ONE L2 instead of all eight
     const int it = (item & 7) * (total >> 3) + (item >> 3);
@@ -214,7 +223,11 @@ __global__ __launch_bounds__(NW * 64, MINW) void vecattn_kernel(VecAttnArgs A) {
     }
   }
   const int i0 = ig * P;
-  __syncthreads();   // previous item's epilogue still reads sidx / the scratch inside X
+  float wmx[TPW * P], wsum[TPW * P], wres[TPW * P];   // MODE 4: running softmax state per (channel tile, query)
+  const int nch = WIDE ? (A.kvalid + 31) >> 5 : 1;
+  int ch = 0;      // MODE 4: the chunk (columns 32 ch ..), looping back to va_chunk from the end of the epilogue
+va_chunk:
+  __syncthreads();   // previous item's (chunk's) epilogue still reads sidx / the scratch inside X
 
   VA_STAMP(0);
   // ---- stage 0: neighbour ids, coordinate deltas, first-layer activations h = relu(W_d1 delta + b_d1) -> X
@@ -226,7 +239,8 @@ __global__ __launch_bounds__(NW * 64, MINW) void vecattn_kernel(VecAttnArgs A) {
     dl[tid * 3 + 0] = 0.01f * (float)jj; dl[tid * 3 + 1] = 0.02f * (float)(qi & 7); dl[tid * 3 + 2] = 0.03f;
     (void)0;
 #else
-    const int id = A.shared_idx ? A.idx[jj] : A.idx[((size_t)b * A.Q + qi) * 32 + jj];
+    const int id = WIDE ? A.idx[((size_t)b * A.Q + qi) * A.ldidx + min(32 * ch + jj, A.kvalid - 1)]
+                        : A.shared_idx ? A.idx[jj] : A.idx[((size_t)b * A.Q + qi) * 32 + jj];
     if (MODE != 2) {
       const float* qx = A.query_xyz + ((size_t)b * A.Q + qi) * 3;
       const float* nx = A.anchor_xyz ? A.anchor_xyz + jj * 3 : A.src_xyz + ((size_t)b * A.NS + id) * 3;
@@ -520,6 +534,11 @@ __global__ __launch_bounds__(NW * 64, MINW) void vecattn_kernel(VecAttnArgs A) {
         for (int i = 0; i < 16; ++i)
           if (mfma_row(i, h) >= A.kvalid) a[i] = -INFINITY;
       }
+      if (WIDE) {
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+          if (32 * ch + mfma_row(i, h) >= A.kvalid) a[i] = -INFINITY;
+      }
       float mx = fmaxf(fmaxf(a[0], a[1]), a[2]);
 #pragma unroll
       for (int i = 3; i < 15; i += 2) mx = fmaxf(fmaxf(mx, a[i]), a[i + 1]);
@@ -539,9 +558,23 @@ __global__ __launch_bounds__(NW * 64, MINW) void vecattn_kernel(VecAttnArgs A) {
       }
       const float sum = half_sum(sum2[0] + sum2[1]);
       const float res = half_sum(res2[0] + res2[1]);
-      if (h == 0 && i0 + p < A.Q) A.out[((size_t)b * A.Q + i0 + p) * C + cch] = res * __builtin_amdgcn_rcpf(sum);
+      if (WIDE) {
+        // online softmax over the chunks: rescale the running and the new partial sums to the common maximum
+        if (ch == 0) {
+          wmx[q] = mx; wsum[q] = sum; wres[q] = res;
+        } else {
+          const float m = fmaxf(wmx[q], mx), nm = -m * k2;
+          const float so = __builtin_amdgcn_exp2f(__builtin_fmaf(wmx[q], k2, nm)), sn = __builtin_amdgcn_exp2f(__builtin_fmaf(mx, k2, nm));
+          wsum[q] = __builtin_fmaf(wsum[q], so, sum * sn);
+          wres[q] = __builtin_fmaf(wres[q], so, res * sn);
+          wmx[q] = m;
+        }
+        if (ch == nch - 1 && h == 0 && i0 + p < A.Q) A.out[((size_t)b * A.Q + i0 + p) * C + cch] = wres[q] * __builtin_amdgcn_rcpf(wsum[q]);
+      } else if (h == 0 && i0 + p < A.Q) A.out[((size_t)b * A.Q + i0 + p) * C + cch] = res * __builtin_amdgcn_rcpf(sum);
     }
   }
+  if constexpr (WIDE)
+    if (++ch < nch) goto va_chunk;
 #undef VA_GATHER
   VA_STAMP(7);
   }   // item loop
@@ -567,6 +600,7 @@ static hipError_t launch_va_t(const VecAttnArgs& a, hipStream_t s) {
 
 template <int C, int P, int NW, int MINW>
 static hipError_t launch_va(const VecAttnArgs& a, hipStream_t s, int mode = 0) {
+  if (mode == 4) return a.composed ? launch_va_t<C, P, NW, MINW, true, 4>(a, s) : launch_va_t<C, P, NW, MINW, false, 4>(a, s);
   if (mode == 1) return launch_va_t<C, P, NW, MINW, true, 1>(a, s);
   if (mode == 2) return launch_va_t<C, P, NW, MINW, true, 2>(a, s);
   if (mode == 3) return a.composed ? launch_va_t<C, P, NW, MINW, true, 3>(a, s) : hipErrorInvalidValue;
@@ -588,6 +622,7 @@ extern "C" void poem_vecattn_one_query_blocks(int on) { g_va_p1 = on; }
 static int va_group_size(int C) { return C == 128 ? 4 : (C >= 512 ? 1 : 2); }
 
 static hipError_t dispatch_va(const VecAttnArgs& a, int C, hipStream_t s, int mode) {
+  if (mode == 4 && (a.kvalid < 1 || a.kvalid > 64 || a.ldidx < a.kvalid || a.shared_idx || a.anchor_xyz)) return hipErrorInvalidValue;
   if (mode == 0 && a.kvalid != 32) {
     if (a.kvalid < 1 || a.kvalid > 32) return hipErrorInvalidValue;
     mode = 3;
@@ -621,7 +656,7 @@ extern "C" hipError_t poem_launch_vector_attention_tables(const float* query_xyz
                                                           const float* bd2, const void* wg1d2, float* tab_g,
                                                           float* tab_p, int Q, int C, hipStream_t s) {
   VecAttnArgs a{query_xyz, nullptr, anchor_xyz, idx, 1, nullptr, nullptr, nullptr, 1, wd1, bd1, (const float4*)wd2, bd2,
-                (const float4*)wg1d2, nullptr, nullptr, nullptr, nullptr, 1, Q, 0, 0, 0, 0, 1, (float4*)tab_g, (float4*)tab_p, 32};
+                (const float4*)wg1d2, nullptr, nullptr, nullptr, nullptr, 1, Q, 0, 0, 0, 0, 1, (float4*)tab_g, (float4*)tab_p, 32, 32};
   return dispatch_va(a, C, s, 1);
 }
 
@@ -631,7 +666,7 @@ extern "C" hipError_t poem_launch_vector_attention_anchored(const int* idx, cons
                                                             const float* tab_g, const float* tab_p, float* out, int B,
                                                             int Q, int C, int ldq, int ldk, int ldv, hipStream_t s) {
   VecAttnArgs a{nullptr, nullptr, nullptr, idx, 1, qg, kg, v, nsrc, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
-                (const float4*)wg2, nullptr, out, B, Q, ldq, ldk, ldv, 0, 1, (float4*)tab_g, (float4*)tab_p, 32};
+                (const float4*)wg2, nullptr, out, B, Q, ldq, ldk, ldv, 0, 1, (float4*)tab_g, (float4*)tab_p, 32, 32};
   return dispatch_va(a, C, s, 2);
 }
 
@@ -642,7 +677,7 @@ extern "C" hipError_t poem_launch_vector_attention(const float* query_xyz, const
                                                    const void* wg2, const float* bg2, float* out, int B, int Q, int C,
                                                    int ldq, int ldk, int ldv, int composed, hipStream_t s) {
   VecAttnArgs a{query_xyz, src_xyz, anchor_xyz, idx, shared_idx, q, k, v, nsrc, wd1, bd1, (const float4*)wd2, bd2,
-                (const float4*)wg1, bg1, (const float4*)wg2, bg2, out, B, Q, ldq, ldk, ldv, 0, composed, nullptr, nullptr, g_va_kvalid};
+                (const float4*)wg1, bg1, (const float4*)wg2, bg2, out, B, Q, ldq, ldk, ldv, 0, composed, nullptr, nullptr, g_va_kvalid, 32};
 #ifdef POEM_LAB
   static const int stagger_env = getenv("POEM_VA_STAGGER") ? atoi(getenv("POEM_VA_STAGGER")) : 0;   // lab only, read once
   a.stagger = stagger_env;
@@ -661,4 +696,15 @@ extern "C" hipError_t poem_launch_vector_attention(const float* query_xyz, const
     }
 #endif
   return dispatch_va(a, C, s, 0);
+}
+
+// MODE 4: K (1..64) neighbours per query from idx (B,Q,ld), ld >= K -- N_NEIGHBOR / N_NEIGHBOR_QUERY above 32.
+extern "C" hipError_t poem_launch_vector_attention_k(const float* query_xyz, const float* src_xyz, const int* idx, int K, int ld,
+                                                     const float* q, const float* k, const float* v, int nsrc, const float* wd1,
+                                                     const float* bd1, const void* wd2, const float* bd2, const void* wg1,
+                                                     const float* bg1, const void* wg2, const float* bg2, float* out, int B, int Q,
+                                                     int C, int ldq, int ldk, int ldv, int composed, hipStream_t s) {
+  VecAttnArgs a{query_xyz, src_xyz, nullptr, idx, 0, q, k, v, nsrc, wd1, bd1, (const float4*)wd2, bd2, (const float4*)wg1, bg1,
+                (const float4*)wg2, bg2, out, B, Q, ldq, ldk, ldv, 0, composed, nullptr, nullptr, K, ld};
+  return dispatch_va(a, C, s, 4);
 }

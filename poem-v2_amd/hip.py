@@ -105,6 +105,9 @@ SIGNATURES = {
     "poem_pck_accumulate": (_i, [_vp, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     "poem_knn": (_i, [_vp, _vp, _vp, _i, _i, _i, _vp]),
     "poem_knn_ex": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "poem_knn_k": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "poem_vector_attention_k": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                     _i, _i, _i, _vp]),
     "poem_vector_attention": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _i, _i, _i, _vp]),
     "poem_reg_update": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
@@ -428,9 +431,15 @@ def cross_attention(q, k, v, heads, split=False, merged=False):
     return ctx
 
 
-def knn(query_xyz, src_xyz, fma=False):
-    """fma=True: distances with the fma contraction of pytorch3d's CUDA kernel (include/poem_hip.h poem_knn_ex)."""
+def knn(query_xyz, src_xyz, fma=False, k=32):
+    """fma=True: distances with the fma contraction of pytorch3d's CUDA kernel (include/poem_hip.h poem_knn_ex).
+    k: the neighbour count, 1..64 (poem_knn_k); -> (B, NQ, k) int32."""
     B, NQ, _ = query_xyz.shape
+    if k != 32:
+        idx = torch.empty(B, NQ, k, dtype=torch.int32, device=query_xyz.device)
+        check(lib().poem_knn_k(ptr(query_xyz), ptr(src_xyz), idx.data_ptr(), B, NQ, src_xyz.shape[1], k, k, int(bool(fma)),
+                               stream()), "poem_knn_k")
+        return idx
     idx = torch.empty(B, NQ, 32, dtype=torch.int32, device=query_xyz.device)
     if fma:
         check(lib().poem_knn_ex(ptr(query_xyz), ptr(src_xyz), idx.data_ptr(), B, NQ, src_xyz.shape[1], 1, stream()), "poem_knn_ex")
@@ -439,9 +448,18 @@ def knn(query_xyz, src_xyz, fma=False):
     return idx
 
 
-def vector_attention(query_xyz, src_xyz, anchor_xyz, idx, q, k, v, wd1, bd1, wd2p, bd2, wg1p, bg1, wg2p, bg2):
+def vector_attention(query_xyz, src_xyz, anchor_xyz, idx, q, k, v, wd1, bd1, wd2p, bd2, wg1p, bg1, wg2p, bg2, nk=None):
+    """nk=None: the 32-column call (poem_vector_attention); nk in 1..64: the first nk columns of idx (B, NQ, ld), ld >= nk
+    (poem_vector_attention_k: src_xyz neighbours, no anchors)."""
     B, NQ, C = q.shape
     out = torch.empty_like(q)
+    if nk is not None:
+        assert idx.dim() == 3 and idx.stride(-1) == 1 and idx.stride(1) == idx.shape[2] and anchor_xyz is None
+        check(lib().poem_vector_attention_k(ptr(query_xyz), ptr(src_xyz), idx.data_ptr(), int(nk), idx.shape[2], ptr(q), ptr(k),
+                                            ptr(v), k.shape[1], ptr(wd1), ptr(bd1), wd2p.data_ptr(), ptr(bd2), wg1p.data_ptr(),
+                                            ptr(bg1), wg2p.data_ptr(), ptr(bg2), ptr(out), B, NQ, C, stream()),
+              "poem_vector_attention_k")
+        return out
     shared = 1 if idx.dim() == 1 else 0
     check(lib().poem_vector_attention(ptr(query_xyz), ptr(src_xyz), ptr(anchor_xyz), idx.data_ptr(), shared, ptr(q), ptr(k),
                                       ptr(v), k.shape[1], ptr(wd1), ptr(bd1), wd2p.data_ptr(), ptr(bd2), wg1p.data_ptr(),

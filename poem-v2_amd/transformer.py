@@ -80,9 +80,10 @@ class PtEmbedTRv4(nn.Module):
         self.nneighbor_query = cfg.N_NEIGHBOR_QUERY
         self.layer_num = cfg.N_BLOCKS
         self.nquery = 799
-        if not (1 <= self.nneighbor <= 32 and 1 <= self.nneighbor_query <= 32):
-            raise NotImplementedError("the MI355X vector attention holds 32 neighbour columns per query: N_NEIGHBOR and "
-                                      "N_NEIGHBOR_QUERY must be in 1..32 (counts below 32 run the masked kernel)")
+        if not (1 <= self.nneighbor <= 64 and 1 <= self.nneighbor_query <= 64):
+            raise NotImplementedError("the MI355X vector attention takes up to two 32-column neighbour tiles per query: "
+                                      "N_NEIGHBOR and N_NEIGHBOR_QUERY must be in 1..64 (below 32: the masked tile; above: two "
+                                      "tiles folded by an online softmax)")
         # BertConfig defaults the reference reads from config/backbone/bert_cfg.json (ptEmb_transformer.py:334)
         self.initializer_range, self.layer_norm_eps = 0.02, 1e-12
         p = os.path.join("config", "backbone", "bert_cfg.json")
