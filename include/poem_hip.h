@@ -69,6 +69,15 @@ extern "C" {
 #define POEM_E_LAUNCH (-3)     /* HIP launch/runtime error (see poem_last_hip_error) */
 #define POEM_E_UNSUPPORTED (-4)
 
+/* Size limits (the kernels address batch-scaled tensors through 32-bit buffer offsets; DESIGN.md "Offsets past 4 GiB"):
+ *   cross attention   batch * nk * embed * 4 < 2^31 (each K / V image below 2 GiB): poem_cross_attention[_merged] return
+ *                     POEM_E_UNSUPPORTED beyond it; poem_head_forward / poem_decoder_forward likewise for
+ *                     batch * nsample * embed * 4 >= 2^31 -- POEM-huge (embed 1024, nsample 4096) up to batch 127,
+ *                     POEM-medium (embed 256) up to 511.
+ *   vector attention  nsrc * embed * 4 (one sample's v rows) below 2 GiB; any batch.
+ *   GEMM              any M: rows past 4 GiB of x run the 64-bit-pointer kernel; poem_gemm_split returns POEM_E_UNSUPPORTED
+ *                     once m * ldx * 4 passes 4 GiB. */
+
 #define POEM_ACT_NONE 0
 #define POEM_ACT_RELU 1
 #define POEM_ACT_GELU 2 /* erf form */

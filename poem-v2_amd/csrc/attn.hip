@@ -883,11 +883,17 @@ extern "C" hipError_t poem_launch_cross_attention_img(const float* q, int ldq, c
                                                       float* scratch, hipStream_t s) {
   return poem_launch_cross_attention_imgq(q, ldq, NQ, kimg, vimg, ctx, B, NQ, NK, C, heads, scratch, s);
 }
+// The kernels address each image through ONE buffer descriptor at its base, with the item's key tile as a signed 32-bit byte
+// offset ((b * nkt + kt0) * ktile_bytes + head / channel-tile offsets, then += adv per tile): exact while an image -- B * NK * C
+// floats -- stays below 2 GiB.  Larger batches are refused here (and by the C ABI up front, include/poem_hip.h).
+extern "C" int poem_cross_attention_fits(int B, int NK, int C) {
+  return (unsigned long long)B * NK * C * 4ull < (1ull << 31);
+}
 extern "C" hipError_t poem_launch_cross_attention_imgq(const float* q, int ldq, int qbr, const void* kimg,
                                                        const void* vimg, float* ctx, int B, int NQ, int NK, int C,
                                                        int heads, float* scratch, hipStream_t s) {
   const int dh = C / heads;
-  if (NK % 32 || C % 32 || (size_t)B * NK * C * 4 >= (1ull << 31)) return hipErrorInvalidValue;
+  if (NK % 32 || C % 32 || !poem_cross_attention_fits(B, NK, C)) return hipErrorInvalidValue;
   const int nqt = (NQ + 31) / 32;
   const int tpc = attn_tiles_per_chunk(NK, dh);
   const int chunks = (NK / 32) / tpc;
@@ -972,7 +978,7 @@ extern "C" int poem_cross_attention_merges(int NK, int C, int heads) {
 extern "C" hipError_t poem_launch_cross_attention_merged(const float* q, int ldq, int qbr, const void* kimg, const void* vimg,
                                                          float* ctx, int B, int NQ, int NK, int C, int heads, hipStream_t s) {
   if (!poem_cross_attention_merges(NK, C, heads) || !ctx) return hipErrorNotSupported;
-  if ((size_t)B * NK * C * 4 >= (1ull << 31)) return hipErrorInvalidValue;
+  if (!poem_cross_attention_fits(B, NK, C)) return hipErrorInvalidValue;
   constexpr int DH = 64, WV = 3, DT = 2;
   const int tpc = attn_tiles_per_chunk(NK, DH), nqt = (NQ + 31) / 32;
   const float kc2 = (float)(1.4426950408889634 / sqrt((double)DH));

@@ -325,6 +325,7 @@ int poem_head_forward(poem_handle_t h, const float* mlvl_feat, const float* cam_
     return POEM_E_ARG;
   const poem_config_t& c = h->cfg;
   if (c.nblocks > 8) return POEM_E_UNSUPPORTED;
+  if (!poem_cross_attention_fits(batch, c.nsample, c.embed)) return POEM_E_UNSUPPORTED;      // batch limit (include/poem_hip.h)
   if (c.parametric && (!pose_aa || !betas)) return POEM_E_ARG;
   if (view_offsets_host[0] != 0 || view_offsets_host[batch] < batch) return POEM_E_ARG;
   SplitContext split_ctx(h);
@@ -364,6 +365,7 @@ int poem_decoder_forward(poem_handle_t h, const float* query_xyz, const float* q
     return POEM_E_ARG;
   const poem_config_t& c = h->cfg;
   if (c.nblocks > 8) return POEM_E_UNSUPPORTED;
+  if (!poem_cross_attention_fits(batch, c.nsample, c.embed)) return POEM_E_UNSUPPORTED;      // batch limit (include/poem_hip.h)
   if (c.parametric && (!pose_aa || !betas)) return POEM_E_ARG;
   Plan p = make_plan(c, batch, batch, workspace, neighbour_ld(c, h->knn_query));
   if (workspace_bytes < p.bytes) return POEM_E_WORKSPACE;

@@ -97,6 +97,7 @@ void poem_cross_attention_split(int on);
 void poem_cross_attention_half(int on);
 void poem_cross_attention_tail_halves(int on);
 int poem_cross_attention_merges(int NK, int C, int heads);
+int poem_cross_attention_fits(int B, int NK, int C);
 hipError_t poem_launch_cross_attention_merged_rm(const float* q, const float* k, const float* v, float* ctx, int B, int NQ, int NK,
                                                  int C, int heads, float* scratch, hipStream_t s);
 hipError_t poem_launch_cross_attention_merged(const float* q, int ldq, int q_batch_rows, const void* kimg, const void* vimg, float* ctx,

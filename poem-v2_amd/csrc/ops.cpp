@@ -107,6 +107,7 @@ size_t poem_cross_attention_scratch_bytes(int batch, int nq, int nk, int embed, 
 int poem_cross_attention(const float* q, const float* k, const float* v, float* ctx, int batch, int nq, int nk, int embed,
                          int heads, void* scratch, size_t scratch_bytes, void* stream) {
   if (!q || !k || !v || !ctx || batch <= 0 || nq <= 0 || nk % 32 || heads <= 0 || embed % heads) return POEM_E_ARG;
+  if (!poem_cross_attention_fits(batch, nk, embed)) return POEM_E_UNSUPPORTED;      // images past 2 GiB (include/poem_hip.h)
   const size_t need = poem_cross_attention_scratch_bytes(batch, nq, nk, embed, heads);
   if (need && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))) return POEM_E_WORKSPACE;
   HIPCHK(poem_launch_cross_attention(q, k, v, ctx, batch, nq, nk, embed, heads, embed, (float*)scratch,
@@ -117,6 +118,7 @@ int poem_cross_attention(const float* q, const float* k, const float* v, float* 
 int poem_cross_attention_merged(const float* q, const float* k, const float* v, float* ctx, int batch, int nq, int nk, int embed,
                                 int heads, void* scratch, size_t scratch_bytes, void* stream) {
   if (!q || !k || !v || !ctx || batch <= 0 || nq <= 0 || nk % 32 || heads <= 0 || embed % heads) return POEM_E_ARG;
+  if (!poem_cross_attention_fits(batch, nk, embed)) return POEM_E_UNSUPPORTED;      // images past 2 GiB (include/poem_hip.h)
   const size_t need = poem_cross_attention_scratch_bytes(batch, nq, nk, embed, heads);
   if (need && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))) return POEM_E_WORKSPACE;
   const hipError_t e = poem_launch_cross_attention_merged_rm(q, k, v, ctx, batch, nq, nk, embed, heads, (float*)scratch, (hipStream_t)stream);

@@ -250,7 +250,7 @@ va_chunk:
     }
 #endif
     sidx[tid] = id;
-    voffs[tid] = (int)(((unsigned)b * (unsigned)A.NS + (unsigned)id) * (unsigned)(A.ldv * 4));
+    voffs[tid] = (int)((unsigned)id * (unsigned)(A.ldv * 4));      // within the sample's rows (dispatch_va bounds it)
   }
   if (MODE != 1)
   for (int f = tid; f < P * C / 4; f += NT) {           // query rows -> LDS (read back as broadcasts in epilogue 1)
@@ -500,7 +500,8 @@ va_chunk:
   //   * the v_j gathers take a 32-bit row offset from LDS (voffs) through a buffer descriptor: one v_add per load.
   float* scr = X + wv * (32 * 33);
   const float k2 = inv_sqrt_c * 1.44269504088896340736f;
-  const __amdgpu_buffer_rsrc_t vrs = frag_rsrc(A.v, 0xffffffffu);
+  // (based at the sample's first v row: a 32-bit offset from A.v wraps once B * NS * ldv * 4 passes 4 GiB)
+  const __amdgpu_buffer_rsrc_t vrs = frag_rsrc(A.v + (size_t)b * A.NS * A.ldv, 0xffffffffu);
   // The v_j gathers of tile q + 1 are issued before tile q's softmax: issued and consumed inside one tile, the L2 / HBM round
   // trip of every tile's sixteen 4-byte gathers stood in front of its weighted sum (vmcnt(14) ... vmcnt(0) in the ISA).
   float vgb[2][16];
@@ -622,6 +623,7 @@ extern "C" void poem_vecattn_one_query_blocks(int on) { g_va_p1 = on; }
 static int va_group_size(int C) { return C == 128 ? 4 : (C >= 512 ? 1 : 2); }
 
 static hipError_t dispatch_va(const VecAttnArgs& a, int C, hipStream_t s, int mode) {
+  if (mode != 1 && (unsigned long long)a.NS * a.ldv * 4 + (unsigned long long)C * 4 > (1ull << 31)) return hipErrorInvalidValue;   // voffs: int
   if (mode == 4 && (a.kvalid < 1 || a.kvalid > 64 || a.ldidx < a.kvalid || a.shared_idx || a.anchor_xyz)) return hipErrorInvalidValue;
   if (mode == 0 && a.kvalid != 32) {
     if (a.kvalid < 1 || a.kvalid > 32) return hipErrorInvalidValue;

@@ -258,7 +258,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void vecattn_split_kernel(VecAttnSpl
       dl[tid * 3 + 1] = qx[1] - nx[1];
       dl[tid * 3 + 2] = qx[2] - nx[2];
       sidx[tid] = id;
-      voffs[tid] = (int)(((unsigned)b * (unsigned)A.NS + (unsigned)id) * (unsigned)(A.ldv * 4));
+      voffs[tid] = (int)((unsigned)id * (unsigned)(A.ldv * 4));      // within the sample's rows (as vecattn.hip)
     }
     for (int f = tid; f < P * C / 4; f += NT) {
       const int p = f / (C / 4), c4 = f % (C / 4);
@@ -362,7 +362,7 @@ __global__ __launch_bounds__(NW * 64, MINW) void vecattn_split_kernel(VecAttnSpl
     __syncthreads();   // X is dead: per-wave transpose scratch from here on
 
     float* scr = reinterpret_cast<float*>(X) + wv * (32 * 33);
-    const __amdgpu_buffer_rsrc_t vrs = frag_rsrc(A.v, 0xffffffffu);
+    const __amdgpu_buffer_rsrc_t vrs = frag_rsrc(A.v + (size_t)b * A.NS * A.ldv, 0xffffffffu);   // the sample's rows
 #pragma unroll
     for (int tp = 0; tp < TPW; ++tp) {
       const int cch = (wv * TPW + tp) * 32 + j;
@@ -438,6 +438,7 @@ extern "C" hipError_t poem_launch_vector_attention_split(const float* query_xyz,
                                                          int ldk, int ldv, hipStream_t s) {
   VecAttnSplitArgs a{query_xyz, src_xyz, anchor_xyz, idx, shared_idx, q, k, v, nsrc, wd1, bd1, wd2, bd2, wg1, wg2, scales,
                      out, B, Q, ldq, ldk, ldv};
+  if ((unsigned long long)nsrc * ldv * 4 + (unsigned long long)C * 4 > (1ull << 31)) return hipErrorInvalidValue;   // voffs: int
   switch (C) {
     case 128: return launch_vs<128, 4, 4, 2>(a, s);
     case 256: {
