@@ -129,6 +129,8 @@ __device__ __forceinline__ void gemm16(const __amdgpu_buffer_rsrc_t wrs, int wba
   if constexpr (RU * T16 <= 2 && KCH % 8 == 0) {
     // small tiles (one or two units of 16 rows: a chunk is 2 RU T16 MFMAs of 32 cycles -- 128 to 256 cycles): weight fragments
     // seven chunks ahead, as lds_gemm.h does for its small tiles and for the same reason (a small batch's tile is a latency chain)
+    // (32-row fragment images only: these tiles take the ring on native images while POEM_C16_RING_MAX >= 2)
+    static_assert(!NAT, "gemm16's small-tile branch reads 32-row fragment images, not native 16x16x4 ones");
     float4 ar[8][T16];
 #define C16_LOADR(D, KCI)                                                                                     \
     {                                                                                                         \

@@ -396,6 +396,30 @@ def test_internal_launcher_declarations_match_their_definitions():
     assert len(decls) >= 30 and not bad, bad
 
 
+def test_chain_args_ctypes_mirror_matches_chain_h():
+    """tests/util.py's ctypes ChainArgs is what test_chain_forms.py hands poem_launch_chain by pointer: a field that drifted
+    from csrc/chain.h (order, name or C type) would make the kernels read garbage pointers.  Parse the struct's declarations
+    and compare them field by field."""
+    import ctypes
+    from util import ChainArgs
+    src = open(os.path.join(ROOT, "poem-v2_amd", "csrc", "chain.h")).read()
+    body = re.search(r"struct ChainArgs\s*\{(.*?)\};", src, re.S).group(1)
+    body = re.sub(r"//[^\n]*", "", body)
+    ctype = {"int": ctypes.c_int, "float": ctypes.c_float, "long long": ctypes.c_longlong}
+    fields = []
+    for decl in (d.strip() for d in body.split(";")):
+        if not decl:
+            continue
+        m = re.match(r"^((?:const\s+)?[A-Za-z_][\w ]*?)\s*(\*?)\s*([A-Za-z_]\w*)$", decl.split(",")[0].strip())
+        assert m, decl
+        base, star = m.group(1).replace("const", "").strip(), m.group(2)
+        names = [m.group(3)] + [n.strip().lstrip("*").strip() for n in decl.split(",")[1:]]
+        for n in names:
+            fields.append((n, ctypes.c_void_p if star else ctype[base]))
+    assert len(fields) == 39, fields
+    assert [(n, t) for n, t in ChainArgs._fields_] == fields
+
+
 def test_bench_refuses_to_report_n_gpus_from_fewer_devices():
     """``python bench.py --gpus N`` without a launcher starts its own ranks; with fewer than N devices it must fail loudly,
     never print a line that claims N GPUs (here: no GPU at all)."""

@@ -1,4 +1,5 @@
 """Shared helpers for the parity tests (test infrastructure)."""
+import ctypes
 import json
 import os
 
@@ -200,3 +201,18 @@ def stage_report(z, spec, tap, oracle_taps):
                 "path_clean": float(dg[rows].max()) if bool(rows.any()) else 0.0,
                 "oracle_clean": float(do[rows].max()) if bool(rows.any()) else 0.0, "clean_rows": float(rows.float().mean())}
     return rep
+
+
+# ---- ctypes mirror of ChainArgs (poem-v2_amd/csrc/chain.h), field for field: the argument block of poem_launch_chain, which
+# tests/test_chain_forms.py passes by pointer.  tests/test_host_logic.py holds this list against the header.
+_P, _I, _F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
+
+
+class ChainArgs(ctypes.Structure):
+    _fields_ = [("kind", _I), ("M", _I), ("tile_p", _I), ("x", _P), ("ldx", _I),
+                ("part_o", _P), ("part_ml", _P), ("pc_heads", _I), ("pc_chunks", _I), ("pc_nq", _I), ("pc_kc2", _F),
+                ("w1", _P), ("b1", _P), ("res", _P), ("ldres", _I), ("res_mod", _I), ("ln_g", _P), ("ln_b", _P), ("eps", _F),
+                ("y1", _P), ("ldy1", _I), ("w2", _P), ("b2", _P), ("n2", _I), ("y2", _P), ("ldy2", _I),
+                ("wf4", _P), ("bf4", _P), ("wreg2", _P), ("breg2", _P), ("xyz_in", _P), ("xyz_out", _P), ("wout", _P), ("bout", _P),
+                ("ln2_g", _P), ("ln2_b", _P), ("y3", _P), ("ldy3", _I),
+                ("native_delta", ctypes.c_longlong)]
