@@ -70,11 +70,12 @@ extern "C" {
 #define POEM_E_UNSUPPORTED (-4)
 
 /* Size limits (the kernels address batch-scaled tensors through 32-bit buffer offsets; DESIGN.md "Offsets past 4 GiB"):
- *   cross attention   batch * nk * embed * 4 < 2^31 (each K / V image below 2 GiB): poem_cross_attention[_merged] return
- *                     POEM_E_UNSUPPORTED beyond it; poem_head_forward / poem_decoder_forward likewise for
- *                     batch * nsample * embed * 4 >= 2^31 -- POEM-huge (embed 1024, nsample 4096) up to batch 127,
- *                     POEM-medium (embed 256) up to 511.
- *   vector attention  nsrc * embed * 4 (one sample's v rows) below 2 GiB; any batch.
+ *   cross attention   batch * nkp * embed * 4 < 2^31 with nkp = 32 * ceil(nk / 32), the keys a sample owns in the K / V
+ *                     images (each image below 2 GiB): poem_cross_attention[_merged] return POEM_E_UNSUPPORTED beyond it;
+ *                     poem_head_forward / poem_decoder_forward likewise for batch * SP * embed * 4 >= 2^31 with
+ *                     SP = 32 * ceil(nsample / 32) -- POEM-huge (embed 1024, nsample 4096) up to batch 127, POEM-medium
+ *                     (embed 256) up to 511; at nsample 8192 half of that.
+ *   vector attention  SP * embed * 4 (one sample's v rows) below 2 GiB; any batch.
  *   GEMM              any M: rows past 4 GiB of x run the 64-bit-pointer kernel; poem_gemm_split returns POEM_E_UNSUPPORTED
  *                     once m * ldx * 4 passes 4 GiB. */
 
@@ -85,7 +86,10 @@ extern "C" {
 typedef struct poem_config {
   int32_t embed;       /* C: EMBED_DIMS = POINTS_FEAT_DIM = INPUT_FEAT_DIM (32..1024, multiple of 32) */
   int32_t in_channels; /* IN_CHANNELS (160), multiple of 8 */
-  int32_t nsample;     /* S: N_SAMPLE (4096); S % C == 0 (Q1 re-interpretation) */
+  int32_t nsample;     /* S: N_SAMPLE (4096).  Any count with max(knn, 1 + max(anchor_idx)) <= S <= 8192.  S % C != 0 (a row of
+                          the Q1 re-interpretation straddles channel lines) takes the operator sampling front end instead of the
+                          fused one; S % 32 != 0 pads a sample's basis-point rows behind the sampling stage to whole 32-key
+                          tiles and runs the masked forms of the cross attention (fp32 precision only). */
   int32_t nquery;      /* Q: 799 */
   int32_t heads;       /* NUM_ATTENTION_HEADS (4) */
   int32_t nblocks;     /* N_BLOCKS (3) */
@@ -238,7 +242,9 @@ int poem_set_anchor_tables(poem_handle_t h, int enable);
  *     (w_hi x_hi + w_hi x_lo + w_lo x_hi, fp32 accumulation; csrc/vecattn_split.hip) -- products carry ~22 significant
  *     bits instead of 24; measured MPVPE against the reference fixtures is unchanged at the 1e-5 mm level.  The
  *     ReLU outputs inside the attention MLPs saturate at 937.5 (f16 range after the x64 pre-scale).
- * Returns POEM_E_UNSUPPORTED when the handle has no split images (embed < 128). */
+ * Returns POEM_E_UNSUPPORTED when the handle has no split images (embed < 128), when a neighbour count is not 32, and when
+ * nsample is not a multiple of 32: the split-precision attention kernels have no masked forms (poem_cross_attention_split_f16x3
+ * likewise refuses nk % 32 != 0). */
 #define POEM_PRECISION_FP32 0
 #define POEM_PRECISION_SPLIT_F16X3 1
 /*   POEM_PRECISION_SPLIT_F16X3_ALL (opt-in): additionally every Linear that runs on the panel GEMM kernel (all of them
@@ -328,8 +334,9 @@ int poem_merge_reduce(const float* h2, const int32_t* view_offsets, float* m, in
                       void* stream);
 int poem_merge_finalize(const float* g, const float* y, const int32_t* view_offsets, float* out, int batch,
                         int nsample, int embed, void* stream);
-/* q (B,Q,C) k,v (B,S,C) -> ctx (B,Q,C); softmax(q k^T / sqrt(C/heads)) v per head  (S % 32 == 0, C % 32 == 0,
- * C/heads in {8,16,32,64,128,256}).  k and v are first re-laid into MFMA fragment images, then the key axis is processed
+/* q (B,Q,C) k,v (B,S,C) -> ctx (B,Q,C); softmax(q k^T / sqrt(C/heads)) v per head  (any S >= 1, C % 32 == 0,
+ * C/heads in {8,16,32,64,128,256}).  k and v are first re-laid into MFMA fragment images -- whole 32-key tiles per sample, the
+ * rows behind key S zero-filled and given weight exactly 0 by the kernels' masked forms --, then the key axis is processed
  * in fixed chunks whose partial (O, m, l) triples are merged in fixed order (a sample's result does not depend on the
  * batch it travels in); images and partials live in `scratch` (poem_cross_attention_scratch_bytes() bytes, 16-byte
  * aligned).  Inside the decoder the projection GEMM writes the images itself. */
@@ -478,7 +485,8 @@ int poem_vector_attention_split(const float* query_xyz, const float* src_xyz, co
                                 const float* bd1, const void* wd2_image, const float* bd2, const void* wg1d2_image,
                                 const void* wg2_image, const float* scales, float* out, int batch, int nq, int embed,
                                 void* stream);
-/* idx (B,Q,32) int32: 32 nearest src points per query, ascending squared L2, ties -> lower index. */
+/* idx (B,Q,32) int32: 32 nearest src points per query, ascending squared L2, ties -> lower index.  32 <= nsrc <= 8192 (a sample's
+ * source coordinates are staged in LDS; poem_knn_k: 1 <= nsrc <= 8192); POEM_E_ARG beyond. */
 int poem_knn(const float* query_xyz, const float* src_xyz, int32_t* idx, int batch, int nq, int nsrc, void* stream);
 /* The same with a choice of the distance's rounding.  fma_contract = 0: ((dx*dx + dy*dy) + dz*dz), every operation rounded --
  * pytorch3d's CPU kernel (knn_cpu.cpp, built without FMA), the path BASELINE's parity bar is stated against, and what

@@ -14,3 +14,4 @@ from .model import PtEmbedMultiviewStereoV2  # noqa: F401
 from .transform import TRANSFORM, SimpleTransform3DMultiView, build_transform  # noqa: F401
 from .wds import MultiviewWebDataset, MixWebDataset, collation_random_n_views  # noqa: F401
 from .mano import ManoLayer  # noqa: F401
+from .hip import make_basis  # noqa: F401

@@ -48,6 +48,12 @@ struct DecoderRun {
   const float *pt_xyz, *pt_feats;
   float *pose_aa, *betas;
   const int B, C, S, Q, BS, BQ;
+  // Rows per sample of the basis-point tensors (pt_feats, the six F1 outputs, pt_xyz_rows): SP = 32 ceil(S / 32).  S itself when
+  // it is a multiple of 32; else run() copies the caller's dense tensors into the plan's padded ones (zero pad rows).  The
+  // neighbour searches read the dense coordinates -- S real sources, so no pad row is ever gathered -- and the cross attentions
+  // take the key count S: their MASK forms drop the SP - S columns of the last key tile (attn.hip).
+  const int SP, BSP;
+  const float* pt_xyz_rows;      // coordinates at SP rows per sample, for the vector cross attention's gathers
   const bool ov;            // side streams in use
   hipStream_t s, sb, sk;    // query side (caller's), basis-point side, neighbour searches
   const bool tables;        // block 0 on the anchor tables (head path, fp32)
@@ -78,7 +84,7 @@ struct DecoderRun {
   DecoderRun(poem_handle_t h_, Plan& p_, const float* feats_in, const float* pt_xyz_, const float* pt_feats_, int B_, float* pose,
              float* bet, hipStream_t s_, bool template_queries)
       : h(h_), p(p_), c(h_->cfg), pt_xyz(pt_xyz_), pt_feats(pt_feats_), pose_aa(pose), betas(bet), B(B_), C(c.embed), S(c.nsample),
-        Q(c.nquery), BS(B_ * c.nsample), BQ(B_ * c.nquery), ov(h_->overlap && h_->bps_stream && h_->knn_stream), s(s_),
+        Q(c.nquery), BS(B_ * c.nsample), BQ(B_ * c.nquery), SP(padded_samples(c)), BSP(B_ * padded_samples(c)), pt_xyz_rows(pt_xyz_), ov(h_->overlap && h_->bps_stream && h_->knn_stream), s(s_),
         sb(ov ? h_->bps_stream : s_), sk(ov ? h_->knn_stream : s_),
         tables(template_queries && h_->anchor_tables && h_->precision == POEM_PRECISION_FP32),
         chain(h_->chains && h_->precision == POEM_PRECISION_FP32 && poem_chain_supported(c.embed) != 0), feats(feats_in),
@@ -125,17 +131,17 @@ struct DecoderRun {
   // features (embedding and fc1 composed in); the four BERT blocks leave the GEMM as MFMA fragment images
   int basis_point_side(int i) {
     const auto& f = h->fused[i];
-    const size_t seg = (size_t)BS * C;
+    const size_t seg = (size_t)BSP * C;
     float* outs[6] = {p.y1[i], p.y1[i] + seg, p.y1[i] + 2 * seg, p.y1[i] + 3 * seg, p.y1[i] + 4 * seg, p.y1[i] + 5 * seg};
     const int modes[6] = {1, 2, 1, 2, 0, 0};
-    h->kv_presplit[i] = poem_gemm_split_applies(f.w[0], BS, C, C) != 0;      // split GEMM -> the K / V images are split too
+    h->kv_presplit[i] = poem_gemm_split_applies(f.w[0], BSP, C, C) != 0;      // split GEMM -> the K / V images are split too
     const bool anchored = tables && i == 0;
     if (!anchored && h->f1_split && C % 128 == 0) {
-      HIPCHK(poem_launch_gemm_segs(pt_feats, C, f.w[0], f.b[0], BS, C, POEM_ACT_NONE, C, 4, outs, modes, sb));
-      HIPCHK(poem_launch_gemm_segs(pt_feats, C, (const float*)f.w[0] + (size_t)4 * C * C, f.b[0] + 4 * C, BS, C, POEM_ACT_NONE, C, 2, outs + 4,
+      HIPCHK(poem_launch_gemm_segs(pt_feats, C, f.w[0], f.b[0], BSP, C, POEM_ACT_NONE, C, 4, outs, modes, sb));
+      HIPCHK(poem_launch_gemm_segs(pt_feats, C, (const float*)f.w[0] + (size_t)4 * C * C, f.b[0] + 4 * C, BSP, C, POEM_ACT_NONE, C, 2, outs + 4,
                                    modes + 4, sb));
     } else {
-      HIPCHK(poem_launch_gemm_segs(pt_feats, C, f.w[0], f.b[0], BS, C, POEM_ACT_NONE, C, anchored ? 4 : 6, outs, modes, sb));
+      HIPCHK(poem_launch_gemm_segs(pt_feats, C, f.w[0], f.b[0], BSP, C, POEM_ACT_NONE, C, anchored ? 4 : 6, outs, modes, sb));
     }
     if (ov) HIPCHK(hipEventRecord(h->ev_bps[i], sb));      // the cross attentions wait for the K / V images only
     if (anchored && !side_rest_pending) return basis_point_anchor_rows(f);
@@ -145,7 +151,7 @@ struct DecoderRun {
     {
       // the vector cross attention of block 0 reads only the 32 anchor rows of (kc | vc): project just those (the same
       // fma chain per element as the full GEMM's rows); its own event: the first cross attention does not wait for them
-      HIPCHK(poem_launch_gather_anchor_rows(pt_feats, C, h->anchor_idx, S, p.anch_x[1], B, C, p.ident, sb));
+      HIPCHK(poem_launch_gather_anchor_rows(pt_feats, C, h->anchor_idx, SP, p.anch_x[1], B, C, p.ident, sb));
       HIPCHK(poem_launch_gemm(p.anch_x[1], C, (const float*)f.w[0] + (size_t)4 * C * C, f.b[0] + 4 * C, nullptr, 0,
                               p.anch_kv[1], 2 * C, B * 32, 2 * C, C, POEM_ACT_NONE, sb));
       if (ov) HIPCHK(hipEventRecord(h->ev_xyz[0], sb));    // (ev_xyz[0]: block 0 has no neighbour search to use it for)
@@ -249,7 +255,7 @@ struct DecoderRun {
         a.x = nullptr; a.part_o = (const float4*)part_o; a.part_ml = (const float2*)part_ml;
         a.pc_heads = c.heads; a.pc_chunks = pchunks; a.pc_nq = Q; a.pc_kc2 = pkc2;
       };
-      HIPCHK(attention(q0, 2 * C, q_batch, p.y1[i], p.y1[i] + (size_t)BS * C));
+      HIPCHK(attention(q0, 2 * C, q_batch, p.y1[i], p.y1[i] + (size_t)BSP * C));
       if (side_rest_pending) {                                               // (a)
         side_rest_pending = false;
         if (tables && i == 0)
@@ -265,7 +271,7 @@ struct DecoderRun {
       ca.ln_g = h->R(a1 + 8); ca.ln_b = h->R(a1 + 9); ca.y1 = p.h_attn; ca.ldy1 = C;
       ca.w2 = (const float4*)h->P(a2 + 0); ca.b2 = h->R(a2 + 1); ca.n2 = 1; ca.y2 = p.qp; ca.ldy2 = C;
       HIPCHK(poem_launch_chain(&ca, C, s));
-      HIPCHK(attention(p.qp, C, Q, p.y1[i] + (size_t)2 * BS * C, p.y1[i] + (size_t)3 * BS * C));
+      HIPCHK(attention(p.qp, C, Q, p.y1[i] + (size_t)2 * BSP * C, p.y1[i] + (size_t)3 * BSP * C));
       if (const int rc = deferred_basis_point_side(i, 2); rc != POEM_OK) return rc;
       ChainArgs cb = chain_args(0);
       cb.x = p.ctx; cb.ldx = C;
@@ -299,10 +305,10 @@ struct DecoderRun {
       if (ov && a == 0) HIPCHK(hipStreamWaitEvent(s, h->ev_bps[i], 0));
       if (h->precision == POEM_PRECISION_SPLIT_F16X3_ALL) poem_cross_attention_split(h->kv_presplit[i] ? 2 : 1);
       if (h->precision == POEM_PRECISION_FP32 && merge_in_attention() && poem_cross_attention_merges(S, C, c.heads))
-        HIPCHK(poem_launch_cross_attention_merged(qptr, ldq, Q, p.y1[i] + (size_t)(2 * a) * BS * C, p.y1[i] + (size_t)(2 * a + 1) * BS * C,
+        HIPCHK(poem_launch_cross_attention_merged(qptr, ldq, Q, p.y1[i] + (size_t)(2 * a) * BSP * C, p.y1[i] + (size_t)(2 * a + 1) * BSP * C,
                                                   p.ctx, B, Q, S, C, c.heads, s));
       else
-        HIPCHK(poem_launch_cross_attention_img(qptr, ldq, p.y1[i] + (size_t)(2 * a) * BS * C, p.y1[i] + (size_t)(2 * a + 1) * BS * C,
+        HIPCHK(poem_launch_cross_attention_img(qptr, ldq, p.y1[i] + (size_t)(2 * a) * BSP * C, p.y1[i] + (size_t)(2 * a + 1) * BSP * C,
                                                p.ctx, B, Q, S, C, c.heads, p.attn_scratch, s));
       const int rc = gemm(p.ctx, C, ab + 6, ab + 7, hidden, ldh, p.att, C, BQ, C, C, POEM_ACT_NONE);
       if (rc != POEM_OK) return rc;
@@ -385,22 +391,22 @@ struct DecoderRun {
     if (h->precision != POEM_PRECISION_FP32) {
       if (kc != 32) return POEM_E_UNSUPPORTED;
       const auto& sw = h->split[2 * i + 1];
-      HIPCHK(poem_launch_vector_attention_split(xyz, pt_xyz, anchor, idx_c, shared, p.qc, p.y1[i] + 4 * (size_t)BS * C,
-                                                p.y1[i] + 5 * (size_t)BS * C, S, h->R(vcb + 4), h->R(vcb + 5), sw.w[0],
+      HIPCHK(poem_launch_vector_attention_split(xyz, pt_xyz_rows, anchor, idx_c, shared, p.qc, p.y1[i] + 4 * (size_t)BSP * C,
+                                                p.y1[i] + 5 * (size_t)BSP * C, SP, h->R(vcb + 4), h->R(vcb + 5), sw.w[0],
                                                 h->R(vcb + 7), sw.w[1], sw.w[2], sw.scales, p.rc, B, Q, C, C, C, C, s));
     } else if (tables && i == 0) {
       if (ov) HIPCHK(hipStreamWaitEvent(s, h->ev_xyz[0], 0));      // the anchor rows of (kc | vc), basis_point_side(0)
       HIPCHK(poem_launch_vector_attention_anchored(p.ident, p.qc, p.anch_kv[1], p.anch_kv[1] + C, 32, h->P(vcb + 10), p.tab_g[1],
                                                    p.tab_p[1], p.rc, B, Q, C, C, 2 * C, 2 * C, s));
     } else if (!shared && p.idx_ld != 32) {             // N_NEIGHBOR on neighbour rows of stride 64 (vecattn.hip MODE 4)
-      HIPCHK(poem_launch_vector_attention_k(xyz, pt_xyz, idx_c, kc, p.idx_ld, p.qc, p.y1[i] + 4 * (size_t)BS * C, p.y1[i] + 5 * (size_t)BS * C,
-                                            S, h->R(vcb + 4), h->R(vcb + 5), h->P(vcb + 6), h->R(vcb + 7), h->fused[i].w[6], h->R(vcb + 9),
+      HIPCHK(poem_launch_vector_attention_k(xyz, pt_xyz_rows, idx_c, kc, p.idx_ld, p.qc, p.y1[i] + 4 * (size_t)BSP * C, p.y1[i] + 5 * (size_t)BSP * C,
+                                            SP, h->R(vcb + 4), h->R(vcb + 5), h->P(vcb + 6), h->R(vcb + 7), h->fused[i].w[6], h->R(vcb + 9),
                                             h->P(vcb + 10), h->R(vcb + 11), p.rc, B, Q, C, C, C, C, 1, s));
     } else {
       poem_vecattn_one_query_blocks(h->va_p1);
       poem_vecattn_valid_neighbours(kc);
-      const hipError_t ve = poem_launch_vector_attention(xyz, pt_xyz, anchor, idx_c, shared, p.qc, p.y1[i] + 4 * (size_t)BS * C,
-                                                         p.y1[i] + 5 * (size_t)BS * C, S, h->R(vcb + 4), h->R(vcb + 5), h->P(vcb + 6),
+      const hipError_t ve = poem_launch_vector_attention(xyz, pt_xyz_rows, anchor, idx_c, shared, p.qc, p.y1[i] + 4 * (size_t)BSP * C,
+                                                         p.y1[i] + 5 * (size_t)BSP * C, SP, h->R(vcb + 4), h->R(vcb + 5), h->P(vcb + 6),
                                                          h->R(vcb + 7), h->fused[i].w[6], h->R(vcb + 9), h->P(vcb + 10), h->R(vcb + 11), p.rc, B,
                                                          Q, C, C, C, C, 1, s);
       poem_vecattn_valid_neighbours(32);
@@ -483,6 +489,13 @@ struct DecoderRun {
   }
 
   int run() {
+    if (SP != S) {      // dense (B, S, .) -> (B, SP, .) with zero pad rows, in front of the fork: both side streams read them
+      if (h->precision != POEM_PRECISION_FP32) return POEM_E_UNSUPPORTED;      // the split-precision attentions have no MASK form
+      HIPCHK(poem_launch_pad_rows(pt_feats, p.feat_pad, B, S, SP, C, s));
+      HIPCHK(poem_launch_pad_rows(pt_xyz, p.xyz_pad, B, S, SP, 3, s));
+      pt_feats = p.feat_pad;
+      pt_xyz_rows = p.xyz_pad;
+    }
     int rc = fork();
     if (rc != POEM_OK) return rc;
     wmask = (ov && chain) ? (h->wait_merge >= 0 ? h->wait_merge : 3) : 0;

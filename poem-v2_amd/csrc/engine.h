@@ -257,9 +257,16 @@ struct Plan {
   float *canon_xyz, *tab_g[2], *tab_p[2];   // block-0 anchor tables (self, cross) of the head path
   float *anch_x[2], *anch_kv[2], *qeqp0;    // block 0: anchor rows of the key/value sources, their (k | v) rows; F2 on Q rows
   int32_t* ident;
+  // N_SAMPLE not a multiple of 32 (else nullptr): the basis-point features and coordinates with padded_samples() rows per sample,
+  // zero behind the S real ones (decoder.cpp)
+  float *feat_pad, *xyz_pad;
   int idx_ld;      // row stride of idx_self / idx_cross: 32, or 64 when a neighbour count is above 32 (neighbour_ld)
   size_t bytes;
 };
+
+// Basis-point rows per sample behind the sampling stage: whole 32-row tiles (the projection GEMM's attention image epilogues
+// and the attention kernels address a sample's keys by tile).  N_SAMPLE itself when it is a multiple of 32.
+inline int padded_samples(const poem_config_t& c) { return (c.nsample + 31) / 32 * 32; }
 
 // Row stride of the neighbour index buffers for N_NEIGHBOR = c.knn and N_NEIGHBOR_QUERY = knn_query (0: the same): 32 while
 // both are <= 32 (every 32-neighbour launch, tap and workspace size as before), else 64.

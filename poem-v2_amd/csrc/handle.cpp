@@ -224,11 +224,14 @@ int check_config(const poem_config_t* c) {
   if (C < 32 || C > 1024 || (C & (C - 1))) return POEM_E_UNSUPPORTED;       // 32,64,...,1024
   // N_NEIGHBOR: 1..32 in one 32-column attention tile (MODE 0 / 3), 33..64 as two tiles one after the other (vecattn.hip MODE 4)
   if (c->knn < 1 || c->knn > 64) return POEM_E_UNSUPPORTED;
-  if (c->in_channels % 8 || c->nsample % 32 || c->nsample % C) return POEM_E_UNSUPPORTED;
+  // N_SAMPLE: any count up to 8192.  Not a multiple of 32: the decoder's basis-point rows are padded to whole key tiles and the
+  // cross attentions run their MASK forms (decoder.cpp, attn.hip); not a multiple of embed (a Q1 row straddles channel lines):
+  // the operator sampling front end (forward.cpp)
+  if (c->in_channels % 8 || c->nsample < 1 || c->nsample > 8192) return POEM_E_UNSUPPORTED;
   if (c->heads <= 0 || C % c->heads) return POEM_E_UNSUPPORTED;
   const int dh = C / c->heads;
   if (!(dh == 8 || dh == 16 || dh == 32 || dh == 64 || dh == 128 || dh == 256)) return POEM_E_UNSUPPORTED;
-  if (c->nsample > 4096 || c->nquery > 4096 || c->nquery < 33) return POEM_E_UNSUPPORTED;
+  if (c->nquery > 4096 || c->nquery < 33) return POEM_E_UNSUPPORTED;
   if (c->knn > c->nsample || c->knn > c->nquery) return POEM_E_UNSUPPORTED;      // K distinct neighbours among the basis points / queries
   if ((c->feat_h * c->feat_w) % 32) return POEM_E_UNSUPPORTED;
   if (c->max_views < 1 || c->max_views > 64 || c->nblocks < 1) return POEM_E_ARG;
@@ -599,6 +602,8 @@ int poem_set_precision(poem_handle_t h, int mode) {
   if (mode != POEM_PRECISION_FP32 && (!h->split_mem || !h->gemm_split)) return POEM_E_UNSUPPORTED;      // embed < 128
   if (mode != POEM_PRECISION_FP32 && (h->cfg.knn != 32 || (h->knn_query && h->knn_query != 32)))
     return POEM_E_UNSUPPORTED;      // the split-precision vector attention has no masked form (decoder.cpp checks again)
+  if (mode != POEM_PRECISION_FP32 && h->cfg.nsample % 32)
+    return POEM_E_UNSUPPORTED;      // ... nor has the split-precision cross attention one for a partial last key tile
   h->precision = mode;
   return POEM_OK;
 }

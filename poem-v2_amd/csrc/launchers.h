@@ -88,12 +88,14 @@ hipError_t poem_launch_vector_attention_anchored(const int* idx, const float* qg
                                                  int Q, int C, int ldq, int ldk, int ldv, hipStream_t s);
 hipError_t poem_launch_gather_anchor_rows(const float* src, int ld, const int* idx, int NS, float* dst, int B, int C,
                                           int* ident, hipStream_t s);
+hipError_t poem_launch_pad_rows(const float* src, float* dst, int B, int S, int SP, int W, hipStream_t s);
 hipError_t poem_launch_canon_xyz(const float* tmpl, float* out, int n, float radius, hipStream_t s);
 hipError_t poem_launch_pack_split(const float* w, int C, void* img, float* scale_out, hipStream_t s);
 hipError_t poem_launch_pack_split_tiles(const float* w, int N, int K, void* img, float* scales, int scale_stride, hipStream_t s);
 void poem_gemm_split_context(const void* packed, size_t bytes, const void* split, const float* scales);
 void poem_gemm_split_explicit(const void* img, const float* scales);
 void poem_cross_attention_split(int on);
+void poem_cross_attention_masked_form(int on);
 void poem_cross_attention_half(int on);
 void poem_cross_attention_tail_halves(int on);
 int poem_cross_attention_merges(int NK, int C, int heads);

@@ -53,6 +53,25 @@ extern "C" hipError_t poem_launch_gather_anchor_rows(const float* src, int ld, c
   return hipGetLastError();
 }
 
+// A sample's S rows of width W into a block of SP >= S rows, the SP - S rows behind them zero: dst (B, SP, W) <- src (B, S, W).
+// The decoder's basis-point tensors for an N_SAMPLE that is not a multiple of 32 (decoder.cpp): the projection GEMM's attention
+// image epilogues and the attention kernels address a sample's keys as whole 32-row tiles.
+__global__ void pad_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, int S, int SP, int W, long total) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= total) return;
+  const int w = (int)(i % W);
+  const long r = i / W;
+  const int row = (int)(r % SP);
+  const long b = r / SP;
+  dst[i] = row < S ? src[((size_t)b * S + row) * W + w] : 0.f;
+}
+
+extern "C" hipError_t poem_launch_pad_rows(const float* src, float* dst, int B, int S, int SP, int W, hipStream_t s) {
+  const long total = (long)B * SP * W;
+  hipLaunchKernelGGL(pad_rows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src, dst, S, SP, W, total);
+  return hipGetLastError();
+}
+
 __global__ void broadcast_rows_kernel(const float* __restrict__ src, float* __restrict__ dst, long per, long total) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < total) dst[i] = src[i % per];

@@ -100,13 +100,13 @@ int poem_merge_finalize(const float* g, const float* y, const int32_t* view_offs
 }
 
 size_t poem_cross_attention_scratch_bytes(int batch, int nq, int nk, int embed, int heads) {
-  if (batch <= 0 || nq <= 0 || nk % 32 || heads <= 0 || embed % heads) return 0;
+  if (batch <= 0 || nq <= 0 || nk <= 0 || heads <= 0 || embed % heads) return 0;
   return poem_cross_attention_scratch_floats(batch, nq, nk, embed, heads, 1) * sizeof(float);
 }
 
 int poem_cross_attention(const float* q, const float* k, const float* v, float* ctx, int batch, int nq, int nk, int embed,
                          int heads, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!q || !k || !v || !ctx || batch <= 0 || nq <= 0 || nk % 32 || heads <= 0 || embed % heads) return POEM_E_ARG;
+  if (!q || !k || !v || !ctx || batch <= 0 || nq <= 0 || nk <= 0 || heads <= 0 || embed % heads) return POEM_E_ARG;
   if (!poem_cross_attention_fits(batch, nk, embed)) return POEM_E_UNSUPPORTED;      // images past 2 GiB (include/poem_hip.h)
   const size_t need = poem_cross_attention_scratch_bytes(batch, nq, nk, embed, heads);
   if (need && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))) return POEM_E_WORKSPACE;
@@ -117,7 +117,7 @@ int poem_cross_attention(const float* q, const float* k, const float* v, float* 
 
 int poem_cross_attention_merged(const float* q, const float* k, const float* v, float* ctx, int batch, int nq, int nk, int embed,
                                 int heads, void* scratch, size_t scratch_bytes, void* stream) {
-  if (!q || !k || !v || !ctx || batch <= 0 || nq <= 0 || nk % 32 || heads <= 0 || embed % heads) return POEM_E_ARG;
+  if (!q || !k || !v || !ctx || batch <= 0 || nq <= 0 || nk <= 0 || heads <= 0 || embed % heads) return POEM_E_ARG;
   if (!poem_cross_attention_fits(batch, nk, embed)) return POEM_E_UNSUPPORTED;      // images past 2 GiB (include/poem_hip.h)
   const size_t need = poem_cross_attention_scratch_bytes(batch, nq, nk, embed, heads);
   if (need && (!scratch || scratch_bytes < need || ((uintptr_t)scratch & 15))) return POEM_E_WORKSPACE;
@@ -169,6 +169,7 @@ int poem_vector_attention_split(const float* query_xyz, const float* src_xyz, co
 int poem_cross_attention_split_f16x3(const float* q, const float* k, const float* v, float* ctx, int batch, int nq, int nk,
                                      int embed, int heads, void* scratch, size_t scratch_bytes, void* stream) {
   if (heads <= 0 || embed % heads || (embed / heads != 32 && embed / heads != 64)) return POEM_E_UNSUPPORTED;
+  if (nk % 32) return POEM_E_UNSUPPORTED;      // no MASK form of the split-precision kernels
   poem_cross_attention_split(1);
   const int rc = poem_cross_attention(q, k, v, ctx, batch, nq, nk, embed, heads, scratch, scratch_bytes, stream);
   poem_cross_attention_split(0);
@@ -176,21 +177,21 @@ int poem_cross_attention_split_f16x3(const float* q, const float* k, const float
 }
 
 int poem_knn(const float* query_xyz, const float* src_xyz, int32_t* idx, int batch, int nq, int nsrc, void* stream) {
-  if (!query_xyz || !src_xyz || !idx || batch <= 0 || nq <= 0 || nsrc < 32 || nsrc > 4096) return POEM_E_ARG;
+  if (!query_xyz || !src_xyz || !idx || batch <= 0 || nq <= 0 || nsrc < 32 || nsrc > 8192) return POEM_E_ARG;
   HIPCHK(poem_launch_knn(query_xyz, src_xyz, idx, batch, nq, nsrc, 0, (hipStream_t)stream));
   return POEM_OK;
 }
 
 int poem_knn_ex(const float* query_xyz, const float* src_xyz, int32_t* idx, int batch, int nq, int nsrc, int fma_contract,
                 void* stream) {
-  if (!query_xyz || !src_xyz || !idx || batch <= 0 || nq <= 0 || nsrc < 32 || nsrc > 4096 || (fma_contract & ~1)) return POEM_E_ARG;
+  if (!query_xyz || !src_xyz || !idx || batch <= 0 || nq <= 0 || nsrc < 32 || nsrc > 8192 || (fma_contract & ~1)) return POEM_E_ARG;
   HIPCHK(poem_launch_knn(query_xyz, src_xyz, idx, batch, nq, nsrc, fma_contract, (hipStream_t)stream));
   return POEM_OK;
 }
 
 int poem_knn_k(const float* query_xyz, const float* src_xyz, int32_t* idx, int batch, int nq, int nsrc, int k, int ld,
                int fma_contract, void* stream) {
-  if (!query_xyz || !src_xyz || !idx || batch <= 0 || nq <= 0 || nsrc < 1 || nsrc > 4096 || k < 1 || k > 64 || k > nsrc ||
+  if (!query_xyz || !src_xyz || !idx || batch <= 0 || nq <= 0 || nsrc < 1 || nsrc > 8192 || k < 1 || k > 64 || k > nsrc ||
       ld < k || (fma_contract & ~1))
     return POEM_E_ARG;
   HIPCHK(poem_launch_knn_k(query_xyz, src_xyz, idx, batch, nq, nsrc, k, ld, fma_contract, (hipStream_t)stream));

@@ -8,6 +8,7 @@ Plan make_plan(const poem_config_t& c, int B, int BN, void* base, int idx_ld) {
   Arena a(base);
   const size_t C = c.embed, S = c.nsample, Q = c.nquery, HW = (size_t)c.feat_h * c.feat_w;
   const size_t BS = (size_t)B * S, BQ = (size_t)B * Q, VS = (size_t)BN * S;
+  const size_t SP = (size_t)padded_samples(c), BSP = (size_t)B * SP;      // keys / values of the decoder: whole 32-row tiles per sample
   p.offs = a.take<int32_t>(B + 1);
   p.view_sample = a.take<int32_t>(BN);
   p.pe_index = a.take<int32_t>(BN);
@@ -54,7 +55,7 @@ Plan make_plan(const poem_config_t& c, int B, int BN, void* base, int idx_ld) {
     p.feats[i] = a.take<float>(BQ * C);
     p.idx_self[i] = a.take<int32_t>(BQ * idx_ld);
     p.idx_cross[i] = a.take<int32_t>(BQ * idx_ld);
-    p.y1[i] = a.take<float>(BS * C * 6);
+    p.y1[i] = a.take<float>(BSP * C * 6);
   }
   p.q3t = a.take<float>((size_t)B * C);
   p.par = a.take<float>((size_t)B * 106);
@@ -78,6 +79,11 @@ Plan make_plan(const poem_config_t& c, int B, int BN, void* base, int idx_ld) {
     p.petr_f = a.take<float>((size_t)BN * 3 * c.depth_num * HW);
     p.petr_h = a.take<float>((size_t)BN * 2 * C * HW);
     p.petr_tab = a.take<float>((size_t)BN * C * HW);
+  }
+  p.feat_pad = p.xyz_pad = nullptr;
+  if (SP != S) {      // (behind everything else: every other pointer is where it is without them)
+    p.feat_pad = a.take<float>(BSP * C);
+    p.xyz_pad = a.take<float>(BSP * 3);
   }
   p.bytes = align_up(a.off, 256);
   return p;

@@ -190,16 +190,43 @@ def make_config(embed, in_channels=160, nsample=4096, nquery=799, heads=4, nbloc
 def load_assets(nsample, root=None):
     """bps (S,3), anchor (32,3), anchor_idx (32,) -- from ``<root>/assets`` when given/present (the reference reads
     them relative to cwd: ptEmb_head.py:791, point_transformers.py:12-13), else the copies shipped in the package."""
-    for d in ([os.path.join(root, "assets")] if root else []) + [os.path.join(os.getcwd(), "assets"), ASSETS]:
+    dirs = ([os.path.join(root, "assets")] if root else []) + [os.path.join(os.getcwd(), "assets"), ASSETS]
+    short = []
+    for d in dirs:
         if all(os.path.exists(os.path.join(d, f)) for f in ("bps.npy", "anchor.npy", "anchor_idx.npy")):
             bps = np.load(os.path.join(d, "bps.npy")).reshape(-1, 3)
             if bps.shape[0] < nsample:
+                short.append(f"{d} ({bps.shape[0]} points)")
                 continue
             anchor = np.load(os.path.join(d, "anchor.npy")).reshape(-1, 3)
             aidx = np.load(os.path.join(d, "anchor_idx.npy")).reshape(-1)
             return (torch.from_numpy(bps[:nsample].astype(np.float32).copy()),
                     torch.from_numpy(anchor.astype(np.float32).copy()), torch.from_numpy(aidx.astype(np.int64).copy()))
-    raise FileNotFoundError("bps.npy / anchor.npy / anchor_idx.npy not found")
+    raise FileNotFoundError(f"N_SAMPLE = {nsample} needs a basis of at least {nsample} points: bps.npy (with anchor.npy and "
+                            f"anchor_idx.npy beside it) was looked for in {', '.join(dirs)}"
+                            + (f"; too small: {', '.join(short)}" if short else "")
+                            + ".  poem_v2_amd.make_basis(n, radius, seed) draws one to save as bps.npy.")
+
+
+def make_basis(n, radius=0.1, seed=0):
+    """(n, 3) float32 basis points drawn uniformly from the ball of `radius` around the origin: Gaussian directions scaled to
+    radius * u^(1/3) with u uniform on [0, 1) -- the recipe behind the reference's ``assets/bps.npy`` (ptEmb_head.py:773-788
+    upstream).  Seeded and deterministic (numpy's PCG64), so a basis of any N_SAMPLE can be written without the reference tree:
+    ``np.save("assets/bps.npy", make_basis(8192, 0.1, 0)[None])`` (the reference's file layout: (1, n, 3)) -- `radius` is the head's RADIUS_SAMPLE: the file holds the points at
+    that scale, as the reference's does."""
+    n = int(n)
+    if n < 1 or not radius > 0:
+        raise ValueError(f"make_basis: n = {n}, radius = {radius}")
+    rng = np.random.Generator(np.random.PCG64(int(seed)))
+    d = rng.standard_normal((n, 3))
+    norm = np.linalg.norm(d, axis=1, keepdims=True)
+    norm[norm == 0] = 1.0
+    r = float(radius) * np.cbrt(rng.random((n, 1)))
+    pts = (d / norm * r).astype(np.float32)
+    # (rounding to float32 may push a point on the surface a last place out: pull it back)
+    over = np.linalg.norm(pts.astype(np.float64), axis=1) > float(radius)
+    pts[over] = np.nextafter(pts[over], np.float32(0))
+    return pts
 
 
 class Engine:

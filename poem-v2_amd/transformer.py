@@ -124,8 +124,10 @@ class PtEmbedTRv4(nn.Module):
             cfg = hip.make_config(C, heads=self.num_attention_heads, nblocks=self.layer_num,
                                   parametric=self.parametric_output, ln_eps=self.layer_norm_eps,
                                   nsample=self._nsample, knn=self.nneighbor)
-            bps, anchor, aidx = hip.load_assets(self._nsample)
-            eng = hip.Engine(cfg, w, bps, anchor, aidx, torch.zeros(self.nquery, 3), device)
+            # (the decoder never reads the basis -- the caller supplies pt_xyz -- so any pt_xyz.shape[1] runs on the shipped
+            #  assets: only the anchors are taken from them)
+            _, anchor, aidx = hip.load_assets(1)
+            eng = hip.Engine(cfg, w, torch.zeros(self._nsample, 3), anchor, aidx, torch.zeros(self.nquery, 3), device)
             if self.nneighbor_query != self.nneighbor:
                 eng.set_option("knn_query", self.nneighbor_query)
             self._own_engine = (sig, eng)

@@ -3,7 +3,9 @@ in the working tree -- for knn.hip and vecattn.hip by default.  Both versions' s
 and compared kernel by kernel (encodings, addresses and the PC-relative offsets of globals, which move with the code size,
 are left out; the alignment padding after the last s_endpgm too).  Kernels new in the working tree are listed, not compared.
 
-  python tools/k32_code_diff.py [--base REV] [file.hip ...]      exit 1 when a pre-existing kernel changed"""
+  python tools/k32_code_diff.py [--base REV] [file.hip ...]      exit 1 when a pre-existing kernel changed
+  python tools/k32_code_diff.py --base <parent commit> attn.hip gemm.hip knn.hip vecattn.hip      the N_SAMPLE change: the masked attention kernels are new
+                                                                            names (attn_kernels.inc compiled twice), nothing else moves"""
 import argparse
 import difflib
 import os
