@@ -37,6 +37,9 @@
  *   poem_reg_update           reg_branch second Linear + xyz residual (pt_metro_transformer.py:38)
  *   poem_triangulate_dlt      batch_triangulate_dlt_torch + the ragged per-sample loop (lib/utils/triangulation.py:5-45,
  *                             lib/models/POEM.py:284-299) -- the stage that produces reference_joints
+ *   poem_dlt_confidence /     triangulate_dlt (lib/utils/triangulation.py:111-148): the same stage with views selected by a
+ *   poem_heatmap_uv_conf      confidence threshold that drops until two are left, or weighted by confidence; the confidence
+ *                             is the heat map's peak, read out next to the expectation
  *   poem_conv3x3 /            ConvBlock (Conv2d 3x3 + BatchNorm(eval) + ReLU, lib/models/bricks/conv.py:4-45) and the glue
  *   poem_upsample2_concat_pad around it in PtEmbedMultiviewStereoV2.feat_decode / uv_decode (lib/models/POEM.py:167-211:
  *   poem_pool_conv1x1_sigmoid F.interpolate x2 + torch.cat, max_pool2d + uv_out + sigmoid); poem_heatmap_uv is the read-out of
@@ -355,6 +358,26 @@ int poem_triangulate_dlt(const float* uv, const float* cam_intr, const float* ca
  * uv (BN,J,2) in image pixels: normalise by (sum + 1e-6), expectation of (x/Wh, y/Hh), scale by (img_w, img_h). */
 int poem_heatmap_uv(const float* heatmaps, float* uv, int views, int njoints, int hm_h, int hm_w, float img_w, float img_h,
                     void* stream);
+/* The same read-out with the joint's confidence: conf (BN,J) = the maximum of each map (what `confis` of
+ * triangulate_dlt holds, lib/utils/triangulation.py:115), in (0, 1) for sigmoid maps; a NaN pixel gives NaN.  uv has
+ * the bits poem_heatmap_uv writes. */
+int poem_heatmap_uv_conf(const float* heatmaps, float* uv, float* conf, int views, int njoints, int hm_h, int hm_w,
+                         float img_w, float img_h, void* stream);
+/* Confidence-aware ragged DLT -- replaces triangulate_dlt (lib/utils/triangulation.py:111-148) and the per-sample loop
+ * around it.  Arguments as poem_triangulate_dlt, plus conf (BN,J) and the optional sel_count (B,J) DEVICE int32 = the
+ * number of cameras that entered each solve (may be NULL).
+ * mode POEM_DLT_THRESHOLD: per joint a camera is used when conf > threshold; while at most one is and threshold > 0,
+ *   threshold -= 0.05 in fp64 (:134-142) -- and, as upstream mutates its argument inside the joint loop, the lowered
+ *   value is what the following joints of that sample start from.  The pass runs on the device inside the launch.
+ *   threshold <= 64 (NaN refused).  A joint left with fewer than two cameras has no triangulation; sel_count tells.
+ * mode POEM_DLT_WEIGHTED: both rows of view n are scaled by conf[n][j]; no view is dropped; threshold is ignored.
+ * conf == 1 everywhere (weighted), or threshold 0 with positive conf, reproduces poem_triangulate_dlt bit for bit.
+ * njoints <= 4096.  Stream-ordered like every other call: no host synchronisation, no copy. */
+#define POEM_DLT_THRESHOLD 1
+#define POEM_DLT_WEIGHTED 2
+int poem_dlt_confidence(const float* uv, const float* conf, const float* cam_intr, const float* cam_mat,
+                        const int32_t* view_offsets, float* out_xyz, int32_t* sel_count, int batch, int njoints, int invert,
+                        int mode, double threshold, void* stream);
 /* Convolutional glue between the backbone's multi-level features and the head -- replaces
  * PtEmbedMultiviewStereoV2.feat_decode / uv_decode (lib/models/POEM.py:167-211, HRNet branch) built from
  * lib/models/bricks/conv.py ConvBlocks.  The Python mirror (poem_v2_amd/decode.py) chains them exactly as the

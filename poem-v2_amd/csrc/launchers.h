@@ -118,6 +118,9 @@ hipError_t poem_launch_vector_attention_split(const float* query_xyz, const floa
                                               int ldk, int ldv, hipStream_t s);
 hipError_t poem_launch_dlt(const float* uv, const float* intr, const float* mat, const int* offs, float* out, int B, int J,
                            int invert, hipStream_t s);
+hipError_t poem_launch_dlt_confidence(const float* uv, const float* conf, const float* intr, const float* mat,
+                                      const int* offs, float* out, int* sel_count, int B, int J, int invert, int mode,
+                                      double threshold, hipStream_t s);
 hipError_t poem_launch_pa_epe(const float* pred, const float* gt, float* out, int B, int P, hipStream_t s);
 hipError_t poem_launch_pck_accumulate(const float* pred, const float* gt, int B, int P, double vmin, double vmax, int steps,
                                       unsigned int* counts, double* sum, unsigned int* n, float* dist_out, hipStream_t s);
@@ -128,6 +131,8 @@ hipError_t poem_launch_warp_affine(const unsigned char* src, const long long* sr
                                    int OH, int OW, hipStream_t s);
 hipError_t poem_launch_heatmap_uv(const float* hmap, float* uv, int maps, int hh, int hw, float img_w, float img_h,
                                   hipStream_t s);
+hipError_t poem_launch_heatmap_uv_conf(const float* hmap, float* uv, float* conf, int maps, int hh, int hw, float img_w,
+                                       float img_h, hipStream_t s);
 size_t poem_conv3x3_packed_floats(int Cout, int Cin);
 hipError_t poem_launch_upcat_conv3x3(const float* a_half, int Ca, const float* b_full, int Cb, const void* wp, const float* scale,
                                      const float* shift, float* out, int views, int Cout, int H, int W, int relu, long out_ns,

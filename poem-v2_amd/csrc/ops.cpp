@@ -246,6 +246,26 @@ int poem_heatmap_uv(const float* heatmaps, float* uv, int views, int njoints, in
   return POEM_OK;
 }
 
+int poem_heatmap_uv_conf(const float* heatmaps, float* uv, float* conf, int views, int njoints, int hm_h, int hm_w, float img_w,
+                         float img_h, void* stream) {
+  if (!heatmaps || !uv || !conf || views <= 0 || njoints <= 0 || hm_h <= 0 || hm_w <= 0) return POEM_E_ARG;
+  HIPCHK(poem_launch_heatmap_uv_conf(heatmaps, uv, conf, views * njoints, hm_h, hm_w, img_w, img_h, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_dlt_confidence(const float* uv, const float* conf, const float* cam_intr, const float* cam_mat,
+                        const int32_t* view_offsets, float* out_xyz, int32_t* sel_count, int batch, int njoints, int invert,
+                        int mode, double threshold, void* stream) {
+  if (!uv || !conf || !cam_intr || !cam_mat || !view_offsets || !out_xyz || batch <= 0 || njoints <= 0 || njoints > 4096 ||
+      (invert & ~1) || (mode != POEM_DLT_THRESHOLD && mode != POEM_DLT_WEIGHTED))
+    return POEM_E_ARG;
+  // the lowering loop runs (threshold / 0.05) times at most; an infinite or absurd threshold would never get there
+  if (mode == POEM_DLT_THRESHOLD && !(threshold <= 64.0)) return POEM_E_ARG;
+  HIPCHK(poem_launch_dlt_confidence(uv, conf, cam_intr, cam_mat, view_offsets, out_xyz, sel_count, batch, njoints, invert, mode,
+                                    threshold, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 size_t poem_conv3x3_packed_bytes(int cout, int cin) {
   if (cout <= 0 || cin <= 0 || cin % 8) return 0;
   return poem_conv3x3_packed_floats(cout, cin) * sizeof(float);

@@ -219,7 +219,9 @@ class FeatureDecoders:
                                                           hip.stream()), "poem_pool_conv1x1_sigmoid")
         return hm
 
-    def heatmap_stage(self, img_feats, W, H):
-        """-> uv_coord_im (BN,21,2) pixels   [POEM.py:213-222]"""
+    def heatmap_stage(self, img_feats, W, H, return_conf=False):
+        """-> uv_coord_im (BN,21,2) pixels   [POEM.py:213-222]; ``return_conf``: also the (BN,21) heat-map peaks.  Whichever
+        route ``uv_decode`` took (read-out head fused into its last convolution, or two launches), the maps it returns
+        are the same bits, and the confidence is read from them by the launch that reads the expectation."""
         from .triangulation import heatmap_to_uv
-        return heatmap_to_uv(self.uv_decode(img_feats), W, H)
+        return heatmap_to_uv(self.uv_decode(img_feats), W, H, return_conf=return_conf)

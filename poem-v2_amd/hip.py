@@ -83,6 +83,8 @@ SIGNATURES = {
     "poem_cross_attention_split_f16x3": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     "poem_triangulate_dlt": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp, _vp]),
     "poem_heatmap_uv": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
+    "poem_heatmap_uv_conf": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
+    "poem_dlt_confidence": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp]),
     "poem_conv3x3_packed_bytes": (_sz, [_i, _i]),
     "poem_pack_conv3x3": (_i, [_vp, _i, _i, _vp, _vp]),
     "poem_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp]),
@@ -153,6 +155,7 @@ def lib():
 
 
 POEM_E_UNSUPPORTED = -4      # include/poem_hip.h
+DLT_MODES = {"threshold": 1, "weighted": 2}                                  # include/poem_hip.h POEM_DLT_*
 ABI_VERSION = 3              # poem_abi_version(): 2 = poem_config_t with the positional-encoding switches (round 5);
                              # 3 = poem_mano_lbs takes the prepared asset table, poem_attach_mano (round 6)
 

@@ -14,6 +14,9 @@ from .decode import FeatureDecoders
 from .triangulation import triangulate_reference_joints
 
 
+DLT_CONFIDENCE_MODES = ("off", "threshold", "weighted")
+
+
 @MODEL.register_module()
 class PtEmbedMultiviewStereoV2:
 
@@ -29,6 +32,11 @@ class PtEmbedMultiviewStereoV2:
         self.img_backbone = HRNet(cfg.get("BACKBONE", None), device=self.device)  # POEM.py:57
         self.ptEmb_head = build_head(cfg.HEAD, data_preset=preset)                # POEM.py:114
         self.num_preds = self.ptEmb_head.num_preds
+        # confidence-aware DLT (upstream's triangulate_dlt, lib/utils/triangulation.py:111-148): "off" | "threshold" | "weighted"
+        self.dlt_confidence = str(cfg.get("DLT_CONFIDENCE", "off")).lower()
+        self.dlt_threshold = float(cfg.get("DLT_CONFIDENCE_THRESHOLD", 0.5))
+        if self.dlt_confidence not in DLT_CONFIDENCE_MODES:
+            raise ValueError(f"DLT_CONFIDENCE {self.dlt_confidence!r}: expected one of {DLT_CONFIDENCE_MODES}")
         self.decoders = None
 
     # -- weights ----------------------------------------------------------------------------------------------------
@@ -68,7 +76,11 @@ class PtEmbedMultiviewStereoV2:
         H, W = img.shape[-2:]
         img_feats = self.extract_img_feat(img)
         mlvl_feat = self.decoders.feat_decode(img_feats, self.img_backbone.name)            # :267
-        uv_pred = self.decoders.heatmap_stage(img_feats, W, H)                              # :270
+        conf = None
+        if self.dlt_confidence == "off":
+            uv_pred = self.decoders.heatmap_stage(img_feats, W, H)                          # :270
+        else:
+            uv_pred, conf = self.decoders.heatmap_stage(img_feats, W, H, return_conf=True)
         K = batch["target_cam_intr"].reshape(-1, 3, 3).to(self.device)
         T = batch["target_cam_extr"].reshape(-1, 4, 4).to(self.device)
         if BN == batch_size:                                                                # :273,282-283
@@ -77,7 +89,9 @@ class PtEmbedMultiviewStereoV2:
             if views.min() < 2:
                 raise ValueError("a batch mixing single-view and multi-view samples has no DLT solution for the former "
                                  "(upstream's SVD returns the null vector of a rank-2 system there)")
-            ref_joints = triangulate_reference_joints(uv_pred, K, T, views)                 # :284-299
+            ref_joints = triangulate_reference_joints(uv_pred, K, T, views, conf=conf,      # :284-299
+                                                      mode=None if conf is None else self.dlt_confidence,
+                                                      threshold=self.dlt_threshold)
         img_metas = {"inp_img_shape": (H, W), "cam_intr": K, "cam_extr": T, "master_id": batch["master_id"],
                      "cam_view_num": views}
         preds = self.ptEmb_head(mlvl_feat=mlvl_feat, img_metas=img_metas, reference_joints=ref_joints)
@@ -86,6 +100,8 @@ class PtEmbedMultiviewStereoV2:
         centre = j[:, self.center_idx, :].unsqueeze(1)
         preds.update(pred_joints_3d=j, pred_verts_3d=v, pred_joints_3d_rel=j - centre, pred_verts_3d_rel=v - centre,
                      pred_joints_uv=uv_pred, pred_ref_joints_3d=ref_joints)                 # :321-331
+        if conf is not None:
+            preds["pred_joints_conf"] = conf
         return preds
 
     def testing_step(self, batch, step_idx=0, **kwargs):

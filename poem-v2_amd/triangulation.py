@@ -3,7 +3,11 @@
 whole ragged batch instead of a Python loop of per-sample ``torch.linalg.svd`` calls.  No CPU fallback.
 
 ``batch_triangulate_dlt_torch`` keeps the reference function's name, argument meaning and result
-(lib/utils/triangulation.py:5-45); ``triangulate_reference_joints`` is the ragged, path-level form."""
+(lib/utils/triangulation.py:5-45); ``triangulate_reference_joints`` is the ragged, path-level form.
+
+Confidence-aware forms (``poem_heatmap_uv_conf`` + ``poem_dlt_confidence``): ``heatmap_to_uv(..., return_conf=True)`` also
+returns each joint's heat-map peak, ``triangulate_reference_joints(..., conf=, mode=)`` discounts views by it, and
+``triangulate_dlt`` keeps the name, arguments and result of upstream's one-sample function (triangulation.py:111-148)."""
 import numpy as np
 import torch
 
@@ -28,9 +32,17 @@ def _offsets(views, device):
     return hit
 
 
-def triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num):
+def triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num, conf=None, mode=None, threshold=0.5,
+                                 return_count=False, invert=True):
     """uv (BN,J,2) pixel coordinates per view, cam_intr (BN,3,3), cam_extr (BN,4,4) camera->master (the batch's
-    ``target_cam_extr``), cam_view_num (B,) views per sample -> (B,J,3) joints in the master frame."""
+    ``target_cam_extr``), cam_view_num (B,) views per sample -> (B,J,3) joints in the master frame.
+
+    ``mode`` None / "off": every view counts the same (``poem_triangulate_dlt``; ``conf`` is not read).
+    ``mode`` "threshold": upstream's ``triangulate_dlt`` per sample (lib/utils/triangulation.py:111-148): a view enters a
+    joint's solve when ``conf`` (BN,J) > ``threshold``; the threshold drops by 0.05 until two views do, and stays lowered
+    for the sample's following joints.  ``mode`` "weighted": each view's two rows are scaled by its confidence.
+    ``return_count``: also the (B,J) int32 number of views each solve used.  ``invert=False``: ``cam_extr`` is already
+    master->camera.  Both run inside one stream-ordered launch."""
     if not uv.is_cuda:
         raise RuntimeError("triangulate_reference_joints runs on the MI355X HIP path only (no CPU fallback)")
     views = [int(v) for v in cam_view_num]
@@ -41,9 +53,41 @@ def triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num):
     uv, cam_intr, cam_extr = f32(uv), f32(cam_intr), f32(cam_extr)
     out = torch.empty(len(views), J, 3, dtype=torch.float32, device=uv.device)
     offs = _offsets(views, uv.device)
-    hip.check(hip.lib().poem_triangulate_dlt(hip.ptr(uv), hip.ptr(cam_intr), hip.ptr(cam_extr), offs.data_ptr(), len(views),
-                                             J, 1, hip.ptr(out), hip.stream()), "poem_triangulate_dlt")
-    return out
+    if mode in (None, "off"):
+        if return_count:
+            raise ValueError("return_count needs a confidence mode")
+        hip.check(hip.lib().poem_triangulate_dlt(hip.ptr(uv), hip.ptr(cam_intr), hip.ptr(cam_extr), offs.data_ptr(),
+                                                 len(views), J, int(bool(invert)), hip.ptr(out), hip.stream()),
+                  "poem_triangulate_dlt")
+        return out
+    if mode not in hip.DLT_MODES:
+        raise ValueError(f"mode {mode!r}: expected None, 'off', 'threshold' or 'weighted'")
+    if conf is None or tuple(conf.shape) != (BN, J):
+        raise ValueError(f"mode {mode!r} needs conf of shape ({BN}, {J})")
+    threshold = float(threshold)
+    if mode == "threshold" and not threshold <= 64.0:
+        raise ValueError("threshold must be a number <= 64 (confidences lie in (0, 1))")
+    conf = f32(conf)
+    count = torch.empty(len(views), J, dtype=torch.int32, device=uv.device) if return_count else None
+    hip.check(hip.lib().poem_dlt_confidence(hip.ptr(uv), hip.ptr(conf), hip.ptr(cam_intr), hip.ptr(cam_extr), offs.data_ptr(),
+                                            hip.ptr(out), hip.ptr(count, torch.int32), len(views), J, int(bool(invert)),
+                                            hip.DLT_MODES[mode], threshold, hip.stream()), "poem_dlt_confidence")
+    return (out, count) if return_count else out
+
+
+def triangulate_dlt(pts, confis, Ks, Extrs, confi_thres=0.5):
+    """Upstream's signature for one sample (lib/utils/triangulation.py:111-148): pts (N,J,2), confis (N,J), Ks (N,3,3),
+    Extrs (N,4,4) master->camera (used as is), confi_thres -> (J,3).  numpy arrays are taken to the current device and the
+    result comes back as numpy, like upstream's; device tensors give a device tensor."""
+    as_np = isinstance(pts, np.ndarray)
+    dev = torch.device("cuda", torch.cuda.current_device()) if as_np else pts.device
+    t = lambda a: torch.as_tensor(a).to(device=dev, dtype=torch.float32)   # noqa: E731
+    pts_t = t(pts)
+    if pts_t.ndim != 3 or pts_t.shape[-1] != 2:
+        raise ValueError("pts must be (N, J, 2)")
+    out = triangulate_reference_joints(pts_t, t(Ks), t(Extrs), [pts_t.shape[0]], conf=t(confis), mode="threshold",
+                                       threshold=confi_thres, invert=False)[0]
+    return out.cpu().numpy().astype(pts.dtype) if as_np else out
 
 
 def batch_triangulate_dlt_torch(kp2ds, Ks, Extrs):
@@ -60,20 +104,30 @@ def batch_triangulate_dlt_torch(kp2ds, Ks, Extrs):
     return out
 
 
-def heatmap_to_uv(uv_hmap, img_w, img_h):
+def heatmap_to_uv(uv_hmap, img_w, img_h, return_conf=False):
     """uv_hmap (BN,J,Hh,Wh) sigmoid heat maps -> (BN,J,2) pixel coordinates: the read-out at the end of the
-    reference's ``heatmap_stage`` (lib/models/POEM.py:213-222 upstream; integral_heatmap2d, integal_pose.py:194-218)."""
+    reference's ``heatmap_stage`` (lib/models/POEM.py:213-222 upstream; integral_heatmap2d, integal_pose.py:194-218).
+    ``return_conf``: also (BN,J) confidences = each map's maximum, from the same launch (``poem_heatmap_uv_conf``)."""
     if not uv_hmap.is_cuda:
         raise RuntimeError("heatmap_to_uv runs on the MI355X HIP path only (no CPU fallback)")
     h = uv_hmap.to(dtype=torch.float32).contiguous()
     BN, J, Hh, Wh = h.shape
     uv = torch.empty(BN, J, 2, dtype=torch.float32, device=h.device)
+    if return_conf:
+        conf = torch.empty(BN, J, dtype=torch.float32, device=h.device)
+        hip.check(hip.lib().poem_heatmap_uv_conf(hip.ptr(h), hip.ptr(uv), hip.ptr(conf), BN, J, Hh, Wh, float(img_w),
+                                                 float(img_h), hip.stream()), "poem_heatmap_uv_conf")
+        return uv, conf
     hip.check(hip.lib().poem_heatmap_uv(hip.ptr(h), hip.ptr(uv), BN, J, Hh, Wh, float(img_w), float(img_h), hip.stream()),
               "poem_heatmap_uv")
     return uv
 
 
-def reference_joints_from_heatmaps(uv_hmap, cam_intr, cam_extr, cam_view_num, img_w, img_h):
+def reference_joints_from_heatmaps(uv_hmap, cam_intr, cam_extr, cam_view_num, img_w, img_h, mode=None, threshold=0.5):
     """Heat maps of every view -> per-view 2-D joints -> ragged DLT -> (B,J,3) reference joints: the two launches that
-    replace POEM.py:213-222 + :284-299 upstream."""
-    return triangulate_reference_joints(heatmap_to_uv(uv_hmap, img_w, img_h), cam_intr, cam_extr, cam_view_num)
+    replace POEM.py:213-222 + :284-299 upstream.  ``mode`` / ``threshold`` as ``triangulate_reference_joints``: the
+    confidences are the maps' own peaks (still two launches)."""
+    if mode in (None, "off"):
+        return triangulate_reference_joints(heatmap_to_uv(uv_hmap, img_w, img_h), cam_intr, cam_extr, cam_view_num)
+    uv, conf = heatmap_to_uv(uv_hmap, img_w, img_h, return_conf=True)
+    return triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num, conf=conf, mode=mode, threshold=threshold)

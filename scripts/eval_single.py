@@ -109,8 +109,11 @@ def install_template(head, reload, template):
 
 
 def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, batch_size=2, seed=0, verbose=True,
-             pyramid=False, template=None):
+             pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5):
     rank, _, world = pdist.env_world()
+    if dlt_confidence != "off" and not pyramid:
+        raise SystemExit("--dlt-confidence reads the heat maps' peaks: it needs --pyramid or --shards (this scope starts "
+                         "behind the heat-map stage)")
     head_node = pk.CN(cfg["MODEL"]["HEAD"])
     head_node["MAX_VIEWS"] = max(10, int(view_range[1]))
     head = pk.build_head(head_node, data_preset=pk.CN({}))
@@ -162,11 +165,17 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
             if decoders is not None:
                 pyr = [f.to(device) for f in pk.inputs.synthetic_pyramid(sum(views), seed=seed * 100003 + s)]
                 mlvl_feat = decoders.feat_decode(pyr)                                   # POEM.py:267
-                uv_pred = decoders.heatmap_stage(pyr, 256, 256)                         # POEM.py:270
+                if dlt_confidence == "off":
+                    uv_pred = decoders.heatmap_stage(pyr, 256, 256)                     # POEM.py:270
+                else:
+                    uv_pred, conf = decoders.heatmap_stage(pyr, 256, 256, return_conf=True)
                 # random features carry no hand: keep the pipeline honest (the kernels run, their output is consumed)
                 # but triangulate a blend that stays near the synthetic joints so the head sees sane geometry
                 uv = uv + 1e-3 * (uv_pred - uv_pred.mean(dim=1, keepdim=True))
-            if min(views) >= 2:
+            if min(views) >= 2 and dlt_confidence != "off":   # upstream's triangulate_dlt (lib/utils/triangulation.py:111-148)
+                rj = triangulate_reference_joints(uv, metas["cam_intr"], metas["cam_extr"], views, conf=conf,
+                                                  mode=dlt_confidence, threshold=dlt_threshold)
+            elif min(views) >= 2:
                 rj = triangulate_reference_joints(uv, metas["cam_intr"], metas["cam_extr"], views)
             else:                                        # single-view samples take the given joints (POEM.py:282-283)
                 rj = b["reference_joints"].to(device)
@@ -197,7 +206,7 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
 
 
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
-                    n_cams=8, raw_size=(640, 480), template=None):
+                    n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -221,7 +230,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     head_node = dict(cfg["MODEL"]["HEAD"])
     head_node["MAX_VIEWS"] = max(10, int(view_range[1]))
     model = pk.build_model(pk.CN({"TYPE": "PtEmbedMultiviewStereoV2", "HEAD": head_node, "DATA_PRESET": {"CENTER_IDX": 9},
-                                  "DEVICE": str(device)}))
+                                  "DEVICE": str(device), "DLT_CONFIDENCE": dlt_confidence,
+                                  "DLT_CONFIDENCE_THRESHOLD": dlt_threshold}))
     if reload:
         sd = torch.load(reload, map_location="cpu")
         model.load_state_dict(sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd)
@@ -293,10 +303,12 @@ def main(args):
         print("--draw: rendering is outside the hot path and not built (DESIGN.md section 0); metrics only")
     if args.shards:
         res = evaluate_shards(cfg, view_range, args.model, device, args.shards, args.dataset, reload=args.reload,
-                              epoch_size=args.epoch_size, batch_size=args.batch_size, template=args.template)
+                              epoch_size=args.epoch_size, batch_size=args.batch_size, template=args.template,
+                              dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold)
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
-                       batch_size=args.batch_size, pyramid=args.pyramid, template=args.template)
+                       batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
+                       dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold)
     if rank == 0:
         exp_id = f"{args.dataset}_view_{view_range[0]}_{view_range[1]}_{args.model}"
         if args.model == "huge":
@@ -329,5 +341,9 @@ if __name__ == "__main__":
     parser.add_argument("--template", type=str, default=None, metavar="FILE",
                         help="(799,3) zero-pose hand template (.npy / .pt; ManoLayer's zero-pose joints + vertices, centred at "
                              "joint 9).  Required for meaningful metrics with --reload; synthetic otherwise (this build).")
+    parser.add_argument("--dlt-confidence", choices=("off", "threshold", "weighted"), default="off",
+                        help="Discount views by their heat-map peak in the DLT of the reference joints (model key DLT_CONFIDENCE; "
+                             "threshold = upstream's triangulate_dlt).  Needs --pyramid or --shards.")
+    parser.add_argument("--dlt-threshold", type=float, default=0.5, help="confi_thres of --dlt-confidence threshold.")
     parser.add_argument("--batch_size", type=int, default=2, help="--val_batch_size of the reference (lib/opt.py:27-30).")
     main(parser.parse_args())
