@@ -53,6 +53,9 @@
  *                             (lib/data_wds/multiview_wds.py:112-118) -- the image side of the input pipeline
  *   poem_rot6d_to_axis_angle  rot6d_to_aa of get_parametric_output (pt_metro_transformer.py:144-146, lib/utils/transform.py:448-466)
  *   poem_mano_lbs             manotorch ManoLayer.forward (pt_metro_transformer.py:120-124,147-148; ptEmb_head.py:732-736,886-892)
+ *   poem_render_mesh /        DrawingHandCallback's mesh overlay and 2-D skeleton (lib/utils/testing.py:101-192 -> OpenDRRenderer,
+ *   poem_draw_skeleton /      lib/viztools/opendr_renderer.py:11-206, and draw_2d_skeleton, lib/viztools/draw.py:234-336): upstream renders on
+ *   poem_project_points       the host through OpenGL, one view at a time; batch_cam_extr_transf + batch_cam_intr_projection in front of it
  *   poem_head_forward         POEM_Generalized_Head.forward + PtEmbedTRv4.forward (ptEmb_head.py:825-964,
  *                             lib/models/layers/ptEmb_transformer.py:371-376)
  */
@@ -539,6 +542,41 @@ int poem_vector_attention_k(const float* query_xyz, const float* src_xyz, const 
 /* xyz_out = xyz_in + r . W^T + b   (W (3,C) raw) */
 int poem_reg_update(const float* r, const float* w, const float* b, const float* xyz_in, float* xyz_out, int rows,
                     int embed, void* stream);
+
+/* ---- rendering (csrc/render.hip): the device side of `eval_single.py --draw` ------------------------------------------------------
+ * poem_render_mesh draws `nmeshes` meshes per sample (one shared face list) into every view of a ragged batch.
+ *   verts (nmeshes,B,V,3) master frame; faces (F,3); vf_offsets (V+1) / vf_faces (3F): the vertex -> face CSR table (the faces around
+ *   vertex i are vf_faces[vf_offsets[i] .. vf_offsets[i+1]); vertex normals sum the face normals in that order); cam_intr (BN,3,3)
+ *   (fx, fy, cx, cy are read), cam_extr (BN,4,4) camera->master, view_offsets (B+1) DEVICE int32 prefix sums; background
+ *   (BN,H,W,3) uint8 shared by the meshes, or NULL = white; lights (L,6) = position in the CAMERA frame | colour; albedo (3).
+ *   rgb (nmeshes,BN,H,W,3) uint8 = trunc(colour * 255); depth (nmeshes,BN,H,W) camera z, +inf where nothing is hit; face_id int32,
+ *   -1 where nothing is hit; both may be NULL.
+ *   Conventions: the sample point of pixel (x, y) is (x, y) in the intrinsics' pixel coordinates (integers are pixel centres);
+ *   top-left fill rule; nearest depth wins, the lower face index at equal depth; faces with a vertex at z < near_z or without area are
+ *   dropped whole (no clipping); no back-face culling; Lambert shading per vertex, perspective-correct interpolation.
+ *   The view count BN = view_offsets[batch] stays on the device, so the host cannot hold the workspace against it: the call draws
+ *   the first cap = workspace_bytes / poem_render_workspace_bytes(1, nverts, nmeshes) views of every mesh (the workspace is laid
+ *   out for cap views and never addressed past them) and skips those past BN.  Pass poem_render_workspace_bytes(BN, ...) bytes or
+ *   more (8-byte aligned) to draw every view; with fewer, the planes of views cap .. BN-1 in rgb / depth / face_id are left
+ *   untouched.  POEM_E_WORKSPACE when the workspace holds no view.
+ *   vf_offsets has nverts + 1 entries -- for the nverts of THIS call (vertices no face names have empty lists).  rgb, depth and
+ *   face_id must not overlap background or each other.
+ *   Invalid arguments (NULL, non-positive sizes, near_z <= 0) return POEM_E_ARG.  POEM_E_UNSUPPORTED: nlights > 8; h or w > 16384;
+ *   nmeshes > 65535; nverts or nfaces > 2^24; views past 65535 in one call are not drawn.  Image planes are addressed with 64-bit offsets.
+ * poem_project_points: points (B,P,3) master frame -> uv (BN,P,2) pixel coordinates in every view of the point's sample (the vertex
+ *   stage of the renderer alone; total_views <= 65535, npoints <= 2^24).
+ * poem_draw_skeleton: image, out (BN,H,W,3) uint8 (out may be image); joints_uv (BN,21,2) pixels; colours (21,3) in [0,1].  Joint j
+ *   paints a disc of radius 6 px and a capsule of half-width 1.5 px to its parent (the wrist for j = 4k+1, else j-1) over the joints
+ *   before it.  No anti-aliasing.  views <= 65535, h, w <= 16384. */
+size_t poem_render_workspace_bytes(int total_views, int nverts, int nmeshes);
+int poem_render_mesh(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces, const float* cam_intr,
+                     const float* cam_extr, const int32_t* view_offsets, const uint8_t* background, const float* lights, int nlights,
+                     const float* albedo, float near_z, uint8_t* rgb, float* depth, int32_t* face_id, int nmeshes, int batch, int nverts,
+                     int nfaces, int h, int w, void* workspace, size_t workspace_bytes, void* stream);
+int poem_project_points(const float* points, const float* cam_intr, const float* cam_extr, const int32_t* view_offsets, float* uv, int batch,
+                        int npoints, int total_views, void* stream);
+int poem_draw_skeleton(const uint8_t* image, const float* joints_uv, const float* colours, uint8_t* out, int views, int h, int w,
+                       void* stream);
 
 #ifdef __cplusplus
 }

@@ -178,4 +178,12 @@ hipError_t poem_launch_param_rows(const float* verts, const float* joints, float
 hipError_t poem_launch_compose_weight(const float* A, const float* Bm, float* out, int N, int Cm, int K, hipStream_t s);
 hipError_t poem_launch_compose_bias(const float* A, const float* b1, const float* b2, float* out, int N, int Cm,
                                     hipStream_t s);
+hipError_t poem_launch_render_vertices(const float* verts, const int* faces, const int* vf_off, const int* vf_faces, const float* intr,
+                                       const float* extr, const int* view_offsets, const float* lights, int nlights, const float* albedo,
+                                       float* vtx, float* uv_out, int M, int B, int V, int F, int view_cap, hipStream_t s);
+hipError_t poem_launch_render_raster(const float* vtx, const int* faces, const int* view_offsets, const unsigned char* background,
+                                     unsigned char* rgb, float* depth, int* face_id, int M, int B, int V, int F, int H, int W, float near_z,
+                                     int view_cap, hipStream_t s);
+hipError_t poem_launch_skeleton(const unsigned char* image, const float* joints, const float* colours, unsigned char* out, int views, int H,
+                                int W, hipStream_t s);
 }

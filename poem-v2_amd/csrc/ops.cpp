@@ -411,4 +411,54 @@ int poem_warp_affine(const uint8_t* src, const int64_t* src_offsets, const int32
                                  out_w, (hipStream_t)stream));
   return POEM_OK;
 }
+
+// ---- mesh rendering (csrc/render.hip) ------------------------------------------------------------------------------------------
+// workspace of a render: six floats per (mesh, view, vertex) -- linear in the view count, so that the number of views a workspace
+// holds can be read back from its size (the view count itself, view_offsets[batch], lives on the device)
+static size_t render_bytes_per_view(int nverts, int nmeshes) { return (size_t)24 * (size_t)nverts * (size_t)nmeshes; }
+
+size_t poem_render_workspace_bytes(int total_views, int nverts, int nmeshes) {
+  if (total_views <= 0 || nverts <= 0 || nmeshes <= 0) return 0;
+  return (size_t)total_views * render_bytes_per_view(nverts, nmeshes);
+}
+
+int poem_render_mesh(const float* verts, const int32_t* faces, const int32_t* vf_offsets, const int32_t* vf_faces, const float* cam_intr,
+                     const float* cam_extr, const int32_t* view_offsets, const uint8_t* background, const float* lights, int nlights,
+                     const float* albedo, float near_z, uint8_t* rgb, float* depth, int32_t* face_id, int nmeshes, int batch, int nverts,
+                     int nfaces, int h, int w, void* workspace, size_t workspace_bytes, void* stream) {
+  if (!verts || !faces || !vf_offsets || !vf_faces || !cam_intr || !cam_extr || !view_offsets || !lights || !albedo || !rgb || !workspace ||
+      nmeshes <= 0 || batch <= 0 || nverts <= 0 || nfaces <= 0 || h <= 0 || w <= 0 || nlights < 0 || !(near_z > 0.f) ||
+      ((uintptr_t)workspace & 7))
+    return POEM_E_ARG;
+  if (nlights > 8 || h > 16384 || w > 16384 || nmeshes > 65535 || nverts > (1 << 24) || nfaces > (1 << 24)) return POEM_E_UNSUPPORTED;
+  const size_t per_view = render_bytes_per_view(nverts, nmeshes);
+  const size_t cap = workspace_bytes / per_view;
+  if (cap == 0) return POEM_E_WORKSPACE;
+  const int view_cap = (int)(cap < 65535 ? cap : 65535);                 // grid y limit: at most 65535 views per call
+  hipStream_t s = (hipStream_t)stream;
+  float* vtx = (float*)workspace;
+  HIPCHK(poem_launch_render_vertices(verts, faces, vf_offsets, vf_faces, cam_intr, cam_extr, view_offsets, lights, nlights, albedo, vtx, nullptr,
+                                     nmeshes, batch, nverts, nfaces, view_cap, s));
+  HIPCHK(poem_launch_render_raster(vtx, faces, view_offsets, background, rgb, depth, face_id, nmeshes, batch, nverts, nfaces, h, w, near_z,
+                                   view_cap, s));
+  return POEM_OK;
+}
+
+int poem_project_points(const float* points, const float* cam_intr, const float* cam_extr, const int32_t* view_offsets, float* uv, int batch,
+                        int npoints, int total_views, void* stream) {
+  if (!points || !cam_intr || !cam_extr || !view_offsets || !uv || batch <= 0 || npoints <= 0 || total_views <= 0 || ((uintptr_t)uv & 7))
+    return POEM_E_ARG;
+  if (total_views > 65535 || npoints > (1 << 24)) return POEM_E_UNSUPPORTED;
+  HIPCHK(poem_launch_render_vertices(points, nullptr, nullptr, nullptr, cam_intr, cam_extr, view_offsets, nullptr, 0, nullptr, nullptr, uv, 1,
+                                     batch, npoints, 0, total_views, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_draw_skeleton(const uint8_t* image, const float* joints_uv, const float* colours, uint8_t* out, int views, int h, int w,
+                       void* stream) {
+  if (!image || !joints_uv || !colours || !out || views <= 0 || h <= 0 || w <= 0) return POEM_E_ARG;
+  if (views > 65535 || h > 16384 || w > 16384) return POEM_E_UNSUPPORTED;
+  HIPCHK(poem_launch_skeleton(image, joints_uv, colours, out, views, h, w, (hipStream_t)stream));
+  return POEM_OK;
+}
 }  // extern "C"

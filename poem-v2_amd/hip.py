@@ -113,6 +113,11 @@ SIGNATURES = {
     "poem_vector_attention": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                    _i, _i, _i, _vp]),
     "poem_reg_update": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "poem_render_workspace_bytes": (_sz, [_i, _i, _i]),
+    "poem_render_mesh": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _vp, _f, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, _sz,
+                              _vp]),
+    "poem_project_points": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "poem_draw_skeleton": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
 }
 
 _LIB = None

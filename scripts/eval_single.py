@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Single-setting evaluation of the hot path -- the drop-in counterpart of the reference's ``scripts/eval_single.py``.
 
-Same command line (``--cfg --dataset --view_min --view_max --model -g --reload -p --draw``) and the same YAML edits
+Same command line (``--cfg --dataset --view_min --view_max --model -g --reload -p --draw``; ``--draw`` renders on the device and
+needs the mesh topology: ``--faces FILE.npy``, panels under ``--draw-dir``) and the same YAML edits
 (scripts/eval_single.py:63-86 upstream: dataset URL / epoch size / view range, the four size fields derived from the
 model category, PARAMETRIC_OUTPUT for medium_MANO), written back to ``--cfg`` exactly as upstream does.  What differs:
 
@@ -109,7 +110,9 @@ def install_template(head, reload, template):
 
 
 def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, batch_size=2, seed=0, verbose=True,
-             pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5):
+             pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None):
+    """``draw``: a ``DrawingHandCallback`` (rank 0, ``--draw --faces``) called with every batch.  This scope has no images: the panels
+    show the meshes and skeletons over mid-grey views."""
     rank, _, world = pdist.env_world()
     if dlt_confidence != "off" and not pyramid:
         raise SystemExit("--dlt-confidence reads the heat maps' peaks: it needs --pyramid or --shards (this scope starts "
@@ -145,7 +148,7 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
     pa = PAEval(None, mesh_score=True, device=device)                       # lib/models/POEM.py:147 upstream
     pck = dict(VAL_MIN=0.0, VAL_MAX=0.02, STEPS=20)                         # AUCCallback defaults, lib/utils/testing.py:31
     pck_j, pck_v = Joint3DPCK(device=device, EVAL_TYPE="joints_3d", **pck), Vert3DPCK(device=device, EVAL_TYPE="verts_3d", **pck)
-    n_done, t0 = 0, None
+    n_done, t0, t_draw = 0, None, 0.0
     with torch.no_grad():
         for it, s in enumerate(range(lo, hi, batch_size)):
             views = views_all[s:min(s + batch_size, hi)]
@@ -187,13 +190,23 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
             pa.feed(preds[-1, :, :21], gt[:, :21], preds[-1, :, 21:], gt[:, 21:])
             pck_j.feed({"pred_joints_3d": preds[-1, :, :21]}, {"master_joints_3d": gt[:, :21]})
             pck_v.feed({"pred_verts_3d": preds[-1, :, 21:]}, {"master_verts_3d": gt[:, 21:]})
+            if draw is not None:                           # rendering, the copy and the PNG files stay out of samples/s
+                torch.cuda.synchronize(device)
+                t_d = time.perf_counter()
+                img_w, img_h = (int(v) for v in metas.get("inp_img_shape", (256, 256)))
+                draw({"pred_verts_3d": preds[-1, :, 21:].contiguous(), "pred_joints_3d": preds[-1, :, :21].contiguous()},
+                     {"image": torch.zeros(sum(views), 3, img_h, img_w, device=device), "cam_view_num": views,
+                      "target_cam_intr": metas["cam_intr"], "target_cam_extr": metas["cam_extr"],
+                      "master_verts_3d": gt[:, 21:], "master_joints_3d": gt[:, :21]}, it)
+                torch.cuda.synchronize(device)
+                t_draw += (time.perf_counter() - t_d) if it > 0 else 0.0
             if it == 0:                                    # first batch builds the engine; time from the second on
                 torch.cuda.synchronize(device)
                 t0 = time.perf_counter()
             else:
                 n_done += len(views)
     torch.cuda.synchronize(device)
-    dt = time.perf_counter() - t0 if t0 else 0.0
+    dt = time.perf_counter() - t0 - t_draw if t0 else 0.0
     mpvpe.reduce(), mpjpe.reduce(), pa.reduce(), pck_j.reduce(), pck_v.reduce()
     pam = pa.get_measures()
     res = {"dataset_source": "synthetic", "scope": "pyramid->verts" if pyramid else "mlvl_feat->verts", "model": model_type, "embed": embed, "view_range": list(view_range),
@@ -206,7 +219,7 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
 
 
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
-                    n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5):
+                    n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -243,7 +256,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
                          pk.weights.seeded_state_dict(model.ptEmb_head.embed_dims, seed=0),
                          template=load_template(template) if template else pk.inputs.synthetic_template(1234))
     mpvpe, mpjpe = MeanEPE("verts", device=device), MeanEPE("joints", device=device)
-    n, t0, frames = 0, None, []
+    n, t0, frames, steps, t_draw = 0, None, [], [0], [0.0]
 
     def run(frames):
         batch = pk.collation_random_n_views(frames, transform=dset.transform)
@@ -254,6 +267,13 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         gv = batch["master_verts_3d"].reshape(-1, 778, 3).to(device)
         mpjpe.feed(preds["pred_joints_3d"], gj)
         mpvpe.feed(preds["pred_verts_3d"], gv)
+        if draw is not None:                               # kept out of samples/s, as in evaluate()
+            torch.cuda.synchronize(device)
+            t_d = time.perf_counter()
+            draw(preds, batch, steps[0])
+            torch.cuda.synchronize(device)
+            t_draw[0] += (time.perf_counter() - t_d) if t0 is not None else 0.0
+        steps[0] += 1
         return len(frames)
 
     for f in dset:
@@ -269,7 +289,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     if frames:
         n += run(frames)
     torch.cuda.synchronize(device)
-    dt = time.perf_counter() - t0 if t0 else 0.0
+    dt = time.perf_counter() - t0 - t_draw[0] if t0 else 0.0
     mpvpe.reduce(), mpjpe.reduce()
     return {"dataset_source": f"record shards {pattern} (synthetic records)", "scope": "shards->images->verts",
             "model": model_type, "view_range": list(view_range), "samples": int(mpvpe.acc[1].item()),
@@ -299,16 +319,27 @@ def main(args):
         raise SystemExit("eval_single.py needs a GPU: the head runs on the MI355X HIP path only (no CPU fallback)")
     device = torch.device("cuda", local_rank if world > 1 else args.gpu_id)
     torch.cuda.set_device(device)
+    draw = None
     if args.draw and rank == 0:
-        print("--draw: rendering is outside the hot path and not built (DESIGN.md section 0); metrics only")
+        if args.faces:
+            faces = np.load(args.faces)
+            if faces.ndim != 2 or faces.shape[1] != 3 or not np.issubdtype(faces.dtype, np.integer):
+                raise SystemExit(f"--faces: {args.faces} holds {faces.dtype} {faces.shape}, expected an (F,3) integer array")
+            if faces.min() < 0 or faces.max() >= 778:
+                raise SystemExit(f"--faces: vertex ids must lie in [0, 778), found [{faces.min()}, {faces.max()}]")
+            draw = pk.DrawingHandCallback(args.draw_dir, faces)
+            print(f"--draw: panels [input | skeleton | mesh] per frame and view under {args.draw_dir}")
+        else:
+            print("--draw: the renderer needs the mesh topology: pass --faces FILE.npy, an (F,3) integer array (MANO's closed faces are "
+                  "licence-gated, like the template: INTEGRATION.md); metrics only")
     if args.shards:
         res = evaluate_shards(cfg, view_range, args.model, device, args.shards, args.dataset, reload=args.reload,
                               epoch_size=args.epoch_size, batch_size=args.batch_size, template=args.template,
-                              dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold)
+                              dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw)
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
-                       dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold)
+                       dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw)
     if rank == 0:
         exp_id = f"{args.dataset}_view_{view_range[0]}_{view_range[1]}_{args.model}"
         if args.model == "huge":
@@ -321,7 +352,7 @@ def main(args):
         torch.distributed.destroy_process_group()
 
 
-if __name__ == "__main__":
+def build_parser():
     parser = argparse.ArgumentParser(description="Eval Single Setting")
     parser.add_argument("--cfg", type=str, required=True, help="Path to the configuration file.")
     parser.add_argument("--dataset", type=str, required=True, help="Dataset name.")
@@ -346,4 +377,12 @@ if __name__ == "__main__":
                              "threshold = upstream's triangulate_dlt).  Needs --pyramid or --shards.")
     parser.add_argument("--dlt-threshold", type=float, default=0.5, help="confi_thres of --dlt-confidence threshold.")
     parser.add_argument("--batch_size", type=int, default=2, help="--val_batch_size of the reference (lib/opt.py:27-30).")
-    main(parser.parse_args())
+    parser.add_argument("--faces", type=str, default=None, metavar="FILE.npy",
+                        help="(F,3) integer array of the mesh's triangles (on a licensed machine: ManoLayer.get_mano_closed_faces()); "
+                             "with --draw the predicted and ground-truth meshes are rendered into every view on the device.")
+    parser.add_argument("--draw-dir", type=str, default="./draw", help="where --draw writes its panels.")
+    return parser
+
+
+if __name__ == "__main__":
+    main(build_parser().parse_args())
