@@ -56,6 +56,8 @@
  *   poem_render_mesh /        DrawingHandCallback's mesh overlay and 2-D skeleton (lib/utils/testing.py:101-192 -> OpenDRRenderer,
  *   poem_draw_skeleton /      lib/viztools/opendr_renderer.py:11-206, and draw_2d_skeleton, lib/viztools/draw.py:234-336): upstream renders on
  *   poem_project_points       the host through OpenGL, one view at a time; batch_cam_extr_transf + batch_cam_intr_projection in front of it
+ *   poem_loss_terms           PtEmbedMultiviewStereoV2.compute_loss + loss_proj_to_multicam (lib/models/POEM.py:336-466), forward only;
+ *                             the sums LossMetric.feed (lib/metrics/basic_metric.py:63-97) reads with .item() stay on the device
  *   poem_head_forward         POEM_Generalized_Head.forward + PtEmbedTRv4.forward (ptEmb_head.py:825-964,
  *                             lib/models/layers/ptEmb_transformer.py:371-376)
  */
@@ -577,6 +579,48 @@ int poem_project_points(const float* points, const float* cam_intr, const float*
                         int npoints, int total_views, void* stream);
 int poem_draw_skeleton(const uint8_t* image, const float* joints_uv, const float* colours, uint8_t* out, int views, int h, int w,
                        void* stream);
+
+/* ---- loss terms (csrc/loss.hip): the VALUE of the reference's training losses, no backward pass ------------------------------------
+ * poem_loss_terms evaluates every term of PtEmbedMultiviewStereoV2.compute_loss (lib/models/POEM.py:363-466 upstream) for a ragged batch
+ * in one launch plus a one-block finalize; nothing returns to the host.
+ *   coords (B,799,3): the last layer of all_coords_preds (21 joints, then 778 vertices); pred_joints_uv (BN,21,2); pred_pose (B,16,3) and
+ *   pred_shape (B,10) when cfg->parametric (else ignored, may be NULL); master_joints_3d (B,21,3), master_verts_3d (B,778,3),
+ *   target_joints_2d (BN,21,2), cam_intr (BN,3,3), cam_extr (BN,4,4) camera->master (its inverse is taken per view, POEM.py:383),
+ *   view_offsets (B+1) DEVICE int32 prefix sums; mano_pose (BN,16,3) / mano_shape (BN,10) per view, read at the master view's row
+ *   view_offsets[b] (POEM.py:439-444); j_regressor (16,778) MANO's th_J_regressor.  All fp32.
+ *   out: POEM_LOSS_NTERMS doubles in device memory, in the key order of upstream's loss_dict:
+ *     [0] loss_heatmap_joints  mean over (BN,21) of sum_2 ((uv_pred - uv_gt) / scale)^2, scale = sqrt(w^2 + h^2)        (POEM.py:372,377-379)
+ *     [1] loss_3d_joints       MSE (joints_l2) or L1 of the predicted joints                                            (:404)
+ *     [2] loss_3d_joints_from_mesh  the same on mano_to_openpose of the predicted and the ground-truth vertices         (:386-387,403)
+ *     [3] loss_3d_verts        MSE (vertices_l2) or L1; parametric: (pred - c) - (gt - c), c = GROUND-TRUTH joint center_idx (:408-418)
+ *     [4] loss_recon           the weighted sum of [1..3], [5..8]                                                       (:405,419,427,435,448)
+ *     [5] loss_2d_joints       loss_proj_to_multicam: joints into every view of their sample, z = 1e-7 where |z| < 1e-7, the offset to
+ *                              target_joints_2d clamped to +-scale/2, / scale, sum_2 of squares, mean over (BN,21)      (:336-361,422-427)
+ *     [6] loss_2d_verts        the same for the vertices against the projected ground-truth vertices                    (:389-400,430-435)
+ *     [7] loss_pose  [8] loss_shape   MSE against the master views' mano_pose / mano_shape                              (:438-448)
+ *     [9] loss                 heatmap_joints_weight * [0] + [4]                                                        (:381,455)
+ *   Terms upstream does not compute are not computed and come out as 0: [5] / [6] at a zero weight, [7] / [8] unless parametric.
+ *   Every arithmetic step is fp64 (upstream: fp32); fixed-order reduction without floating-point atomics, so a call is reproducible
+ *   bit for bit; a NaN input makes the terms it reaches NaN -- as torch.clamp does -- and leaves the others untouched.
+ *   workspace: poem_loss_workspace_bytes(batch, total_views) bytes, 8-byte aligned, caller-owned (block partials; need not be zeroed).
+ *   POEM_E_ARG: a NULL argument -- j_regressor included: the from-mesh term is part of loss_recon, a silent 0 would be a wrong loss --,
+ *   non-positive sizes, batch > total_views, center_idx outside 0..20, misaligned out / workspace.  POEM_E_UNSUPPORTED: total_views >
+ *   65535.  POEM_E_WORKSPACE: workspace_bytes too small.  None of them launches.  Rows are addressed with 64-bit offsets. */
+#define POEM_LOSS_NTERMS 10
+typedef struct poem_loss_cfg {
+  double joints_weight, vertices_weight, joints_2d_weight, vertices_2d_weight, heatmap_joints_weight; /* LOSS.*_WEIGHT (POEM.py:125-129) */
+  double pose_weight, shape_weight;             /* POSE_LOSS_WEIGHT, SHAPE_LOSS_WEIGHT (:130-131) */
+  int32_t joints_l2, vertices_l2;               /* JOINTS_LOSS_TYPE / VERTICES_LOSS_TYPE == "l2": MSELoss, else L1Loss (:133-141) */
+  int32_t parametric;                           /* HEAD.TRANSFORMER.PARAMETRIC_OUTPUT (:44) */
+  int32_t center_idx;                           /* TRANSFORMER_CENTER_IDX (:45) */
+  int32_t img_h, img_w;                         /* gt["image"].size(-2), .size(-1) (:369-370) */
+} poem_loss_cfg_t;
+size_t poem_loss_workspace_bytes(int batch, int total_views);
+int poem_loss_terms(const float* coords, const float* pred_joints_uv, const float* pred_pose, const float* pred_shape,
+                    const float* master_joints_3d, const float* master_verts_3d, const float* target_joints_2d, const float* cam_intr,
+                    const float* cam_extr, const int32_t* view_offsets, const float* mano_pose, const float* mano_shape,
+                    const float* j_regressor, const poem_loss_cfg_t* cfg, int batch, int total_views, double* out, void* workspace,
+                    size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ registers them, as ``import lib.models`` does upstream)."""
 from .config import CN  # noqa: F401
 from .builder import (HEAD, TRANSFORMER, BACKBONE, MODEL, Registry, build_from_cfg, build_head, build_transformer,  # noqa: F401
                       build_backbone, build_model)
-from . import builder, weights, inputs, hip, configs, triangulation, decode, backbone, transform, wds, mano, render  # noqa: F401
+from . import builder, weights, inputs, hip, configs, triangulation, decode, backbone, transform, wds, mano, render, losses  # noqa: F401
 from .transformer import PtEmbedTRv4  # noqa: F401
 from .head import POEM_Generalized_Head  # noqa: F401
 from .backbone import HRNet  # noqa: F401
@@ -16,3 +16,4 @@ from .wds import MultiviewWebDataset, MixWebDataset, collation_random_n_views  #
 from .mano import ManoLayer  # noqa: F401
 from .hip import make_basis  # noqa: F401
 from .render import MeshRenderer, DrawingHandCallback, draw_skeleton, project_to_views, save_png  # noqa: F401
+from .losses import PoemLoss, LossMetric  # noqa: F401

@@ -21,3 +21,13 @@ def head_cfg(embed=256, nsample=4096, parametric=False, max_views=10):
 def model_head_cfg(model="medium", **kw):
     """model in {small, medium, large, huge, medium_MANO} (scripts/eval_single.py:38-39 upstream)."""
     return head_cfg(MODEL_EMBED[model], parametric=(model == "medium_MANO"), **kw)
+
+
+def loss_cfg(**kw):
+    """The release ``MODEL.LOSS`` node (config/release/train_medium.yaml:226-235 upstream; the same in every train_*.yaml).
+    TRIANGULATED_JOINTS_WEIGHT and EDGE_LOSS_WEIGHT are listed there but compute_loss never reads them (lib/models/POEM.py:125-131)."""
+    node = {"JOINTS_LOSS_TYPE": "l2", "VERTICES_LOSS_TYPE": "l1", "HEATMAP_JOINTS_WEIGHT": 10.0, "TRIANGULATED_JOINTS_WEIGHT": 10.0,
+            "JOINTS_LOSS_WEIGHT": 1.0, "VERTICES_LOSS_WEIGHT": 1.0, "JOINTS_2D_LOSS_WEIGHT": 1.0, "VERTICES_2D_LOSS_WEIGHT": 0.0,
+            "EDGE_LOSS_WEIGHT": 0.0}
+    node.update(kw)
+    return CN(node)

@@ -108,7 +108,9 @@ static inline size_t packed_linear_floats(int N, int K) { return (size_t)((N + 3
 // ---- shared by the input kernels of the whole path (misc.hip prep_xyz_kernel, sample.hip invert_extr_kernel, merge.hip
 // input_tables_kernel) --------------------------------------------------------------------------------------------------------
 // inverse of a camera->master 4x4: fp64 Gauss-Jordan with partial pivoting, rounded to fp32 (torch.linalg.inv's role, collation.py:56-61)
-__device__ inline void invert4x4(const float* __restrict__ m, float* __restrict__ out) {
+// (Out = double keeps the fp64 result: loss.hip, whose every step is fp64)
+template <typename Out>
+__device__ inline void invert4x4(const float* __restrict__ m, Out* __restrict__ out) {
   double a[4][8];
   for (int i = 0; i < 4; ++i)
     for (int j = 0; j < 4; ++j) { a[i][j] = (double)m[i * 4 + j]; a[i][4 + j] = (i == j) ? 1.0 : 0.0; }
@@ -124,7 +126,7 @@ __device__ inline void invert4x4(const float* __restrict__ m, float* __restrict_
       for (int j = 0; j < 8; ++j) a[i][j] -= f * a[c][j];
     }
   }
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) out[i * 4 + j] = (float)a[i][4 + j];
+  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) out[i * 4 + j] = (Out)a[i][4 + j];
 }
 
 // element i of the coordinate normalisation (see prep_xyz_kernel): centre = reference_joints[:, 9]; pt_xyz = ((bps + c) - c) / radius;

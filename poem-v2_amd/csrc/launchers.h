@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "chain.h"
+#include "loss.h"
 #include "merge.h"
 
 extern "C" {
@@ -186,4 +187,6 @@ hipError_t poem_launch_render_raster(const float* vtx, const int* faces, const i
                                      int view_cap, hipStream_t s);
 hipError_t poem_launch_skeleton(const unsigned char* image, const float* joints, const float* colours, unsigned char* out, int views, int H,
                                 int W, hipStream_t s);
+// loss.hip: every term of compute_loss in one launch + a one-block finalize
+hipError_t poem_launch_loss_terms(const LossArgs* a, hipStream_t s);
 }

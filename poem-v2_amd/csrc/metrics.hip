@@ -2,6 +2,7 @@
 // batch to the host (`.cpu().numpy()`, lib/metrics/pa_eval.py:48-49, pck.py:48-53) and loops over samples in Python /
 // scipy; here one launch per batch accumulates into small device buffers that are read once at the end.
 #include "common.h"
+#include "mano_tables.h"
 
 // ---- Procrustes-aligned end-point error --------------------------------------------------------------------------
 // PAEval.align_w_scale (lib/metrics/pa_eval.py:104-124): centre both point sets, scale each to unit Frobenius norm
@@ -137,8 +138,7 @@ extern "C" hipError_t poem_launch_pck_accumulate(const float* pred, const float*
 // {744, 320, 443, 555, 672} (CONST.MANO_KPID_2_VERTICES, lib/utils/misc.py:76-82), concatenated and re-ordered to the
 // OpenPose numbering.  testing_step applies it to predicted AND ground-truth vertices of every batch (POEM.py:602-603).
 // One wave per (sample, output joint); lane-strided partial sums in a fixed order -> batch-independent results.
-__constant__ int kOpenposeFromMano[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-__constant__ int kTipVertex[5] = {744, 320, 443, 555, 672};
+// (kOpenposeFromMano / kTipVertex: mano_tables.h, shared with loss.hip)
 
 __global__ __launch_bounds__(64) void mano_to_openpose_kernel(const float* __restrict__ jreg, const float* __restrict__ verts,
                                                               float* __restrict__ joints, int nverts) {

@@ -1,5 +1,6 @@
 // Operator-level entry points of libpoem_hip.so (include/poem_hip.h names the reference call each one replaces): argument
 // checks around the launchers of launchers.h.  Stream-ordered, no allocation.
+#include <cmath>
 #include <cstring>
 #include "engine.h"
 
@@ -459,6 +460,46 @@ int poem_draw_skeleton(const uint8_t* image, const float* joints_uv, const float
   if (!image || !joints_uv || !colours || !out || views <= 0 || h <= 0 || w <= 0) return POEM_E_ARG;
   if (views > 65535 || h > 16384 || w > 16384) return POEM_E_UNSUPPORTED;
   HIPCHK(poem_launch_skeleton(image, joints_uv, colours, out, views, h, w, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+// ---- loss terms (csrc/loss.hip) --------------------------------------------------------------------------------------------------
+// workspace: one double per (block, slot) -- sized for the widest grid (vertices projected), whatever the configuration of a call
+size_t poem_loss_workspace_bytes(int batch, int total_views) {
+  if (batch <= 0 || total_views <= 0) return 0;
+  return sizeof(double) * ((size_t)total_views * LOSS_VIEW_GROUPS * LOSS_VIEW_SLOTS + (size_t)batch * LOSS_SAMPLE_SLOTS);
+}
+
+int poem_loss_terms(const float* coords, const float* pred_joints_uv, const float* pred_pose, const float* pred_shape,
+                    const float* master_joints_3d, const float* master_verts_3d, const float* target_joints_2d, const float* cam_intr,
+                    const float* cam_extr, const int32_t* view_offsets, const float* mano_pose, const float* mano_shape,
+                    const float* j_regressor, const poem_loss_cfg_t* cfg, int batch, int total_views, double* out, void* workspace,
+                    size_t workspace_bytes, void* stream) {
+  static_assert(POEM_LOSS_NTERMS == LOSS_NTERMS, "include/poem_hip.h and csrc/loss.h disagree on the result's layout");
+  // a NULL j_regressor is an error, not a skipped term: upstream always adds the from-mesh joints to loss_recon
+  if (!coords || !pred_joints_uv || !master_joints_3d || !master_verts_3d || !target_joints_2d || !cam_intr || !cam_extr || !view_offsets ||
+      !j_regressor || !cfg || !out || !workspace || batch <= 0 || total_views <= 0 || batch > total_views ||
+      ((uintptr_t)out & 7) || ((uintptr_t)workspace & 7))
+    return POEM_E_ARG;
+  if (cfg->parametric && (!pred_pose || !pred_shape || !mano_pose || !mano_shape)) return POEM_E_ARG;
+  if (cfg->center_idx < 0 || cfg->center_idx > 20 || cfg->img_h <= 0 || cfg->img_w <= 0) return POEM_E_ARG;
+  if (total_views > 65535) return POEM_E_UNSUPPORTED;                       // the renderer's limit on a ragged batch
+  if (workspace_bytes < poem_loss_workspace_bytes(batch, total_views)) return POEM_E_WORKSPACE;
+  LossArgs a{};
+  a.coords = coords, a.pred_uv = pred_joints_uv, a.pred_pose = pred_pose, a.pred_shape = pred_shape;
+  a.gt_joints = master_joints_3d, a.gt_verts = master_verts_3d, a.gt_uv = target_joints_2d;
+  a.intr = cam_intr, a.extr = cam_extr, a.view_offsets = view_offsets;
+  a.mano_pose = mano_pose, a.mano_shape = mano_shape, a.jreg = j_regressor;
+  a.w_joints = cfg->joints_weight, a.w_verts = cfg->vertices_weight, a.w_joints_2d = cfg->joints_2d_weight;
+  a.w_verts_2d = cfg->vertices_2d_weight, a.w_heatmap = cfg->heatmap_joints_weight;
+  a.w_pose = cfg->pose_weight, a.w_shape = cfg->shape_weight;
+  a.img_scale = sqrt((double)cfg->img_w * (double)cfg->img_w + (double)cfg->img_h * (double)cfg->img_h);      // POEM.py:372
+  a.joints_l2 = cfg->joints_l2 != 0, a.verts_l2 = cfg->vertices_l2 != 0, a.parametric = cfg->parametric != 0;
+  a.center_idx = cfg->center_idx;
+  a.B = batch, a.BN = total_views;
+  a.view_groups = cfg->vertices_2d_weight != 0.0 ? LOSS_VIEW_GROUPS : 1;
+  a.part = (double*)workspace, a.out = out;
+  HIPCHK(poem_launch_loss_terms(&a, (hipStream_t)stream));
   return POEM_OK;
 }
 }  // extern "C"

@@ -29,6 +29,16 @@ class PoemConfig(ctypes.Structure):
                 ("depth_end", ctypes.c_double), ("position_range", ctypes.c_double * 6)]
 
 
+class PoemLossCfg(ctypes.Structure):
+    """include/poem_hip.h poem_loss_cfg_t"""
+    _fields_ = [("joints_weight", ctypes.c_double), ("vertices_weight", ctypes.c_double), ("joints_2d_weight", ctypes.c_double),
+                ("vertices_2d_weight", ctypes.c_double), ("heatmap_joints_weight", ctypes.c_double), ("pose_weight", ctypes.c_double),
+                ("shape_weight", ctypes.c_double), ("joints_l2", ctypes.c_int32), ("vertices_l2", ctypes.c_int32),
+                ("parametric", ctypes.c_int32), ("center_idx", ctypes.c_int32), ("img_h", ctypes.c_int32), ("img_w", ctypes.c_int32)]
+
+
+LOSS_NTERMS = 10             # include/poem_hip.h POEM_LOSS_NTERMS
+
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
 _cfgp = ctypes.POINTER(PoemConfig)
 
@@ -118,6 +128,9 @@ SIGNATURES = {
                               _vp]),
     "poem_project_points": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "poem_draw_skeleton": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
+    "poem_loss_workspace_bytes": (_sz, [_i, _i]),
+    "poem_loss_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(PoemLossCfg), _i, _i, _vp,
+                             _vp, _sz, _vp]),
 }
 
 _LIB = None

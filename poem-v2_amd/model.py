@@ -4,13 +4,15 @@ images -> HRNet pyramid -> ``feat_decode`` / ``heatmap_stage`` -> ragged DLT -> 
 
 Which part runs where: the backbone is plain PyTorch-ROCm (backbone.py; out of the hot path), everything after it is
 the HIP path (decode.py, triangulation.py, head.py -> libpoem_hip.so).  Training-mode noise on the reference joints
-(POEM.py:272-281), losses and summaries are not built."""
+(POEM.py:272-281), gradients and summaries are not built; with a ``LOSS`` node in the config,
+``compute_loss`` gives the VALUE of upstream's losses for a forward's ``preds`` (losses.py, forward only)."""
 import numpy as np
 import torch
 
 from .backbone import HRNet
 from .builder import MODEL, CN, build_head
 from .decode import FeatureDecoders
+from .losses import LossMetric, PoemLoss
 from .triangulation import triangulate_reference_joints
 
 
@@ -38,6 +40,13 @@ class PtEmbedMultiviewStereoV2:
         if self.dlt_confidence not in DLT_CONFIDENCE_MODES:
             raise ValueError(f"DLT_CONFIDENCE {self.dlt_confidence!r}: expected one of {DLT_CONFIDENCE_MODES}")
         self.decoders = None
+        # optional LOSS node (POEM.py:41-45,125-146): the loss VALUE of a forward; absent -> compute_loss raises, nothing else changes
+        self.loss = None
+        if cfg.get("LOSS", None) is not None:
+            tr = cfg.HEAD.get("TRANSFORMER", CN({}))
+            self.loss = PoemLoss(cfg.LOSS, parametric=bool(tr.get("PARAMETRIC_OUTPUT", False)),
+                                 transformer_center_idx=int(tr.get("TRANSFORMER_CENTER_IDX", 9)))
+        self.loss_metric = LossMetric(cfg)                                        # POEM.py:146 (allocates at its first feed)
 
     # -- weights ----------------------------------------------------------------------------------------------------
     def load_state_dict(self, sd):
@@ -58,6 +67,20 @@ class PtEmbedMultiviewStereoV2:
             self.ptEmb_head.set_template(template)
         self.ptEmb_head.to(self.device).eval()
         return self
+
+    # -- losses (value only) ------------------------------------------------------------------------------------------
+    def set_j_regressor(self, j_regressor):
+        """MANO's ``th_J_regressor`` (16,778) for ``loss_3d_joints_from_mesh`` -- an input, the asset is licence-gated."""
+        if self.loss is None:
+            raise RuntimeError("set_j_regressor: the model was built without a LOSS node")
+        self.loss.set_j_regressor(j_regressor)
+        return self
+
+    def compute_loss(self, preds, gt):
+        """``(loss, loss_dict)`` of upstream's ``compute_loss`` (POEM.py:363-466) as 0-dim fp64 device tensors; no backward pass."""
+        if self.loss is None:
+            raise RuntimeError("compute_loss: the model was built without a LOSS node (cfg.LOSS, as in config/release/train_*.yaml)")
+        return self.loss(preds, gt)
 
     # -- forward ----------------------------------------------------------------------------------------------------
     def extract_img_feat(self, img):

@@ -2,7 +2,8 @@
 """Single-setting evaluation of the hot path -- the drop-in counterpart of the reference's ``scripts/eval_single.py``.
 
 Same command line (``--cfg --dataset --view_min --view_max --model -g --reload -p --draw``; ``--draw`` renders on the device and
-needs the mesh topology: ``--faces FILE.npy``, panels under ``--draw-dir``) and the same YAML edits
+needs the mesh topology: ``--faces FILE.npy``, panels under ``--draw-dir``; ``--losses --j-regressor FILE.npy`` with ``--shards`` adds the
+averages of upstream's loss terms to the result line) and the same YAML edits
 (scripts/eval_single.py:63-86 upstream: dataset URL / epoch size / view range, the four size fields derived from the
 model category, PARAMETRIC_OUTPUT for medium_MANO), written back to ``--cfg`` exactly as upstream does.  What differs:
 
@@ -81,6 +82,24 @@ def default_cfg():
     head = plain(pk.configs.head_cfg(256))
     head.pop("MAX_VIEWS", None)
     return {"DATASET": {"TEST": {"TARGET": {}}}, "MODEL": {"TYPE": "PtEmbedMultiviewStereoV2", "HEAD": head}}
+
+
+def loss_node(cfg):
+    """The ``LOSS`` node of the evaluated config when it has one, else the release values (config/release/train_medium.yaml:226-235
+    upstream, restated in ``poem_v2_amd.configs.loss_cfg``)."""
+    node = cfg.get("MODEL", {}).get("LOSS")
+    return dict(node) if node else dict(pk.configs.loss_cfg())
+
+
+def check_losses_args(args):
+    if not args.losses:
+        return
+    if not args.shards:
+        raise SystemExit("--losses needs --shards: the loss terms read target_joints_2d and the heat maps' 2-D joints, which only the "
+                         "record-shard scope has")
+    if not args.j_regressor:
+        raise SystemExit("--losses needs --j-regressor FILE.npy: MANO's th_J_regressor (16,778) for loss_3d_joints_from_mesh -- an input, "
+                         "the asset is licence-gated (INTEGRATION.md)")
 
 
 def random_views(n_samples, view_range, seed):
@@ -219,12 +238,14 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
 
 
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
-                    n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None):
+                    n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
     (``PtEmbedMultiviewStereoV2``: HRNet on PyTorch-ROCm -> decode / heat maps / DLT / head on HIP) and the device metrics
     against the records' ``master_joints_3d`` / ``master_verts_3d`` (lib/models/POEM.py:596-610 upstream).
+    ``losses``: MANO's (16,778) joint regressor (``--losses --j-regressor``): every batch's loss terms (upstream's ``compute_loss``,
+    value only) feed the model's ``loss_metric`` on the device and the result gains their batch-size-weighted averages.
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
     shards of the same record layout are written there first."""
     rank, _, world = pdist.env_world()
@@ -242,9 +263,13 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     dset = pk.MultiviewWebDataset(node, data_preset=node.DATA_PRESET, is_train=False, defer_images=True, rank=rank, world=world)
     head_node = dict(cfg["MODEL"]["HEAD"])
     head_node["MAX_VIEWS"] = max(10, int(view_range[1]))
-    model = pk.build_model(pk.CN({"TYPE": "PtEmbedMultiviewStereoV2", "HEAD": head_node, "DATA_PRESET": {"CENTER_IDX": 9},
-                                  "DEVICE": str(device), "DLT_CONFIDENCE": dlt_confidence,
-                                  "DLT_CONFIDENCE_THRESHOLD": dlt_threshold}))
+    model_node = {"TYPE": "PtEmbedMultiviewStereoV2", "HEAD": head_node, "DATA_PRESET": {"CENTER_IDX": 9}, "DEVICE": str(device),
+                  "DLT_CONFIDENCE": dlt_confidence, "DLT_CONFIDENCE_THRESHOLD": dlt_threshold}
+    if losses is not None:
+        model_node["LOSS"] = loss_node(cfg)
+    model = pk.build_model(pk.CN(model_node))
+    if losses is not None:
+        model.set_j_regressor(losses)
     if reload:
         sd = torch.load(reload, map_location="cpu")
         model.load_state_dict(sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd)
@@ -267,6 +292,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         gv = batch["master_verts_3d"].reshape(-1, 778, 3).to(device)
         mpjpe.feed(preds["pred_joints_3d"], gj)
         mpvpe.feed(preds["pred_verts_3d"], gv)
+        if losses is not None:                             # one launch + finalize, sums stay on the device (POEM.py:476,483 upstream)
+            model.loss_metric.feed(model.compute_loss(preds, batch)[1], len(frames))
         if draw is not None:                               # kept out of samples/s, as in evaluate()
             torch.cuda.synchronize(device)
             t_d = time.perf_counter()
@@ -291,15 +318,19 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     torch.cuda.synchronize(device)
     dt = time.perf_counter() - t0 - t_draw[0] if t0 else 0.0
     mpvpe.reduce(), mpjpe.reduce()
-    return {"dataset_source": f"record shards {pattern} (synthetic records)", "scope": "shards->images->verts",
-            "model": model_type, "view_range": list(view_range), "samples": int(mpvpe.acc[1].item()),
-            "MPVPE_mm_vs_record_gt": mpvpe.result() * 1e3, "MPJPE_mm_vs_record_gt": mpjpe.result() * 1e3,
-            "samples_per_s_rank0": (n / dt) if dt > 0 and n else None, "world_size": world,
-            "template_source": template_source}
+    res = {"dataset_source": f"record shards {pattern} (synthetic records)", "scope": "shards->images->verts",
+           "model": model_type, "view_range": list(view_range), "samples": int(mpvpe.acc[1].item()),
+           "MPVPE_mm_vs_record_gt": mpvpe.result() * 1e3, "MPJPE_mm_vs_record_gt": mpjpe.result() * 1e3,
+           "samples_per_s_rank0": (n / dt) if dt > 0 and n else None, "world_size": world,
+           "template_source": template_source}
+    if losses is not None:
+        res["losses"] = model.loss_metric.reduce().get_measures()
+    return res
 
 
 def main(args):
     view_range = [args.view_min, args.view_max]
+    check_losses_args(args)
     if args.cfg and os.path.exists(args.cfg):
         with open(args.cfg, "r") as f:
             cfg = yaml.load(f, Loader=yaml.FullLoader)
@@ -332,10 +363,16 @@ def main(args):
         else:
             print("--draw: the renderer needs the mesh topology: pass --faces FILE.npy, an (F,3) integer array (MANO's closed faces are "
                   "licence-gated, like the template: INTEGRATION.md); metrics only")
+    j_regressor = None
+    if args.losses:
+        j_regressor = np.load(args.j_regressor)
+        if j_regressor.shape != (16, 778):
+            raise SystemExit(f"--j-regressor: {args.j_regressor} holds {j_regressor.dtype} {j_regressor.shape}, expected (16,778)")
     if args.shards:
         res = evaluate_shards(cfg, view_range, args.model, device, args.shards, args.dataset, reload=args.reload,
                               epoch_size=args.epoch_size, batch_size=args.batch_size, template=args.template,
-                              dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw)
+                              dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw,
+                              losses=j_regressor)
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
@@ -381,6 +418,12 @@ def build_parser():
                         help="(F,3) integer array of the mesh's triangles (on a licensed machine: ManoLayer.get_mano_closed_faces()); "
                              "with --draw the predicted and ground-truth meshes are rendered into every view on the device.")
     parser.add_argument("--draw-dir", type=str, default="./draw", help="where --draw writes its panels.")
+    parser.add_argument("--losses", action="store_true",
+                        help="with --shards: evaluate upstream's loss terms (compute_loss, value only) on the device for every batch and "
+                             "add their averages to the result line.  Needs --j-regressor.")
+    parser.add_argument("--j-regressor", type=str, default=None, metavar="FILE.npy",
+                        help="(16,778) float array: MANO's th_J_regressor (on a licensed machine: ManoLayer.th_J_regressor), read by "
+                             "loss_3d_joints_from_mesh.")
     return parser
 
 
