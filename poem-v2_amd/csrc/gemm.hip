@@ -158,7 +158,10 @@ __global__ __launch_bounds__(256, 2) void gemm2_kernel(const float* __restrict__
 #pragma unroll
   for (int i = 0; i < MT; ++i) {
     if (IN_PA) {
-      xp[i] = reinterpret_cast<const float4*>(X) + (size_t)(mt0 + i) * KC * 64 + lane;
+      // (tile clamp: with MT = 2 and an odd number of row tiles the last wave's second tile lies past the ceil(M/32)*32 rows
+      //  of the PA buffer; like the row clamp below it re-reads the last tile, and that tile's accumulators are never stored)
+      const int mt = min(mt0 + i, (M + 31) / 32 - 1);
+      xp[i] = reinterpret_cast<const float4*>(X) + (size_t)mt * KC * 64 + lane;
     } else {
       const int row = min((mt0 + i) * 32 + r, M - 1);
       xp[i] = reinterpret_cast<const float4*>(X + (size_t)row * ldx + 4 * h);
@@ -878,6 +881,8 @@ static hipError_t launch_panel_t(const float* X, int ldx, const void* Wp, const 
   return hipGetLastError();
 }
 
+// (tests/gemm_forms_util.py mirrors the choices made from here down to poem_launch_gemm2 -- panel NT / MT / xcd_map, K-slab MT, the
+//  gemm2 tile -- and tests/test_gemm_forms.py asserts the branch of each of its cases with it: a change here changes the mirror too)
 static hipError_t launch_gemm_split_impl(const float* X, int ldx, const void* Wp, const float* bias, const float* R,
                                          int ldr, float* Y, int ldy, int M, int N, int K, int act, int act_split,
                                          int act2, const PanelSegs& segs, hipStream_t s) {

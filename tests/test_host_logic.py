@@ -431,3 +431,80 @@ def test_bench_refuses_to_report_n_gpus_from_fewer_devices():
                          capture_output=True, text=True, env=env, timeout=300)
     assert out.returncode != 0 and "refusing" in (out.stderr + out.stdout), (out.stdout[-500:], out.stderr[-500:])
     assert "\"n_gpus\"" not in out.stdout
+
+
+# ---- the plain-Python side of tests/test_gemm_forms.py ---------------------------------------------------------------
+def test_gemm_forms_index_maps_are_bijections():
+    """The PA / K-image and V-image maps cover their buffer exactly once, the two names of the PA order coincide, and a map
+    agrees with the element-by-element statement of the layout comment."""
+    import gemm_forms_util as gu
+    for rows, cols in ((32, 32), (96, 64), (64, 256)):
+        for index in (gu.pa_index, gu.k_image_index, gu.v_image_index):
+            idx = index(rows, cols)
+            assert idx.shape == (rows, cols)
+            assert torch.equal(idx.flatten().sort().values, torch.arange(rows * cols))
+        assert torch.equal(gu.pa_index(rows, cols), gu.k_image_index(rows, cols))
+    pa, vi = gu.pa_index(64, 32), gu.v_image_index(64, 32)
+    for f4 in range(64 * 32 // 4):
+        lane, rest = f4 % 64, f4 // 64
+        mt, kc = divmod(rest, 32 // 8)
+        for e in range(4):
+            assert pa[32 * mt + (lane & 31), 8 * kc + 4 * (lane >> 5) + e] == 4 * f4 + e
+        g, rest = rest % 4, rest // 4
+        mt, vt = divmod(rest, 32 // 32)
+        for e in range(4):
+            assert vi[32 * mt + 8 * g + 4 * (lane >> 5) + e, 32 * vt + (lane & 31)] == 4 * f4 + e
+    assert gu.pa_index(33, 8).max() < gu.image_floats(33, 8) == 64 * 8
+
+
+def test_gemm_forms_dispatch_mirror_on_the_release_shapes():
+    """gemm_forms_util.dispatch for 256 CUs: the decoder's GEMMs at C = 256 (BQ = 25568 rows, 131072 basis-point rows), the
+    POEM-huge shapes of the K-slab kernel, and the fall-backs."""
+    import gemm_forms_util as gu
+    d = lambda *a, **k: gu.dispatch(*a, ncu=256, **k)      # noqa: E731
+    assert d(25568, 256, 256) == ("panel", 2, 2, False, False)
+    assert d(25568, 1280, 256, act=1, act_split=256, act2=2) == ("panel", 4, 2, True, False)
+    assert d(25568, 768, 256) == ("panel", 4, 1, False, False)
+    assert d(131072, 1536, 256, seg_cols=256) == ("panel", 4, 2, False, False)
+    assert d(131072, 1024, 256, seg_cols=256) == ("panel", 4, 2, False, True)
+    assert d(25568, 256, 1024) == ("kslab", 1)
+    assert d(33000, 1024, 1024) == ("kslab", 2)
+    assert d(25568, 256, 1024, kslab=False) == ("gemm2", 2, 4)
+    assert d(799, 256, 256) == ("panel", 1, 1, False, False) and d(799, 256, 256, narrow=False)[:3] == ("panel", 4, 1)
+    assert d(257, 256, 1024) == ("gemm2", 1, 2) and d(33, 96, 160) == ("panel", 1, 1, False, False)
+    assert d(64, 160, 2048, act=1, act_split=32, act2=2) == ("refuse",)
+    assert d(64, 576, 96, act=2, seg_cols=96) == ("refuse",)
+    assert gu.gemm2_branch(6085, 1024) == (2, 4) and gu.gemm2_branch(6000, 1024) == (1, 2) and gu.gemm2_branch(77, 96) == (1, 1)
+    assert gu.panel_passes(799, 256, ("panel", 1, 1, False, False), 256) == 1
+    assert gu.panel_passes(32 * 2049, 32, ("panel", 1, 1, False, False), 256) == 2
+
+
+def test_gemm_forms_restatements_against_torch():
+    """The fp64 / fp32 restatements of test_gemm_forms.py are the operations they claim to be: against torch's linear, gelu, relu and
+    layer_norm in float64 (the fp32 ones within fp32 rounding of it); relu_nan keeps a NaN."""
+    import gemm_forms_util as gu
+    F = torch.nn.functional
+    g = torch.Generator().manual_seed(0)
+    x, w, b, r = torch.randn(70, 48, generator=g), torch.randn(96, 48, generator=g) / 7, torch.randn(96, generator=g), torch.randn(70, 96, generator=g)
+    lin = F.linear(x.double(), w.double(), b.double())
+    want = {0: lin, 1: torch.relu(lin), 2: F.gelu(lin)}
+    for act in (0, 1, 2):
+        assert torch.allclose(gu.gemm_ref(x, w, b, r, act=act), want[act] + r.double(), rtol=0, atol=1e-12)
+        assert float((gu.gemm_ref(x, w, b, r, act=act, fp32=True).double() - want[act] - r.double()).abs().max()) < 2e-5
+    two = gu.gemm_ref(x, w, b, None, act=1, act_split=32, act2=2)
+    assert torch.equal(two[:, :32], want[1][:, :32]) and torch.allclose(two[:, 32:], want[2][:, 32:], rtol=0, atol=1e-12)
+    assert torch.isnan(gu.relu_nan(torch.tensor([float("nan"), -1.0, 2.0]))).tolist() == [True, False, False]
+    xi, wi = torch.randint(-4, 5, (9, 64), generator=g).float(), torch.randint(-4, 5, (5, 64), generator=g).float()
+    assert torch.equal(gu.linear_seq(xi, wi), xi @ wi.T)
+    for cols in (32, 96, 256):
+        t = torch.randn(7, cols, generator=g) * 3 + 100
+        gm, bt = torch.randn(cols, generator=g), torch.randn(cols, generator=g)
+        for eps in (1e-12, 1e-5):
+            ref = F.layer_norm(t.double(), (cols,), gm.double(), bt.double(), eps)
+            assert torch.allclose(gu.layernorm_ref(t, gm, bt, eps), ref, rtol=0, atol=1e-10)
+            assert float((gu.layernorm_ref(t, gm, bt, eps, fp32=True).double() - ref).abs().max()) < 1e-4
+        wn, bn, base = torch.randn(3, cols, generator=g), torch.randn(3, generator=g), torch.randn(7, 3, generator=g)
+        ref = base.double() + F.linear(t.double(), wn.double(), bn.double())
+        assert torch.allclose(gu.narrow_ref(t, wn, bn, base), ref, rtol=0, atol=1e-10)
+        assert float((gu.narrow_ref(t, wn, bn, base, fp32=True).double() - ref).abs().max()) < 2e-3
+        assert torch.allclose(gu.narrow_ref(t, wn), F.linear(t.double(), wn.double()), rtol=0, atol=1e-10)
