@@ -4,6 +4,7 @@
 ``num_preds`` attribute, side effect on ``img_metas["inp_res"]`` and the same ``state_dict`` key names for every
 tensor the forward reads.  The nn.Modules below only hold parameters; all arithmetic runs in libpoem_hip.so through
 one ``poem_head_forward`` call.  There is no CPU / eager fallback."""
+import os
 import warnings
 import weakref
 
@@ -14,7 +15,8 @@ import torch.nn as nn
 from . import hip
 from .builder import HEAD, build_transformer
 from .inputs import synthetic_template
-from .weights import live_key_shapes
+from .mano import mano_assets_from_manotorch, normalise_mano_assets
+from .weights import StrictLoadFilter, live_key_shapes
 
 # Epoch of the process's module TREES: bumped whenever any nn.Module registers a submodule (`head.transformer = ...`,
 # `blocks[1] = ...`, parametrize.register_parametrization, add_module).  The head caches the `_parameters` dicts of its
@@ -32,6 +34,17 @@ def _on_module_registration(module, name, submodule):
 
 
 torch.nn.modules.module.register_module_module_registration_hook(_on_module_registration)
+
+
+def _same_device(a, b):
+    """torch.device("cuda") and torch.device("cuda:0") name the same device when 0 is the current one."""
+    a, b = torch.device(a), torch.device(b)
+    if a.type != b.type:
+        return False
+    if a.type != "cuda":
+        return a.index == b.index
+    cur = torch.cuda.current_device
+    return (cur() if a.index is None else a.index) == (cur() if b.index is None else b.index)
 
 
 @HEAD.register_module()
@@ -85,12 +98,33 @@ class POEM_Generalized_Head(nn.Module):
         # a seeded synthetic template is used until ``set_template`` is called with the real one.
         self.register_buffer("template", synthetic_template(), persistent=False)
         self._template_is_synthetic = True
+        # the template tensor the HEAD installed (the synthetic one, later the one derived from the assets), followed through
+        # .to(); a template the caller gave -- set_template() or `head.template = t` -- is not this object and is never replaced
+        self._own_template = self.template
         self.mano_layer = None    # callable (pose_aa (B,48), betas (B,10)) -> (verts (B,778,3), joints (B,21,3))
         self.max_views = int(cfg.get("MAX_VIEWS", 10))
         self._engine = None          # the engine of the most recent forward
         self._engines = {}           # stream handle -> engine (see _engine_for)
         self._options = {}
         self._engine_sig = None
+        # strict loading of a reference checkpoint: the dead tensors upstream serialises are taken out of
+        # load_state_dict's unexpected keys, whatever module is the root of the call (weights.StrictLoadFilter)
+        self.ignored_reference_keys = []      # what the most recent load_state_dict swallowed, relative to the head
+        self._reference_checkpoint_loaded = False
+        StrictLoadFilter(self, "", self._classifier_kw, self._note_ignored)
+        # MANO assets (five arrays): set_mano_assets() > the MANO_ASSETS config key > an importable manotorch, built with
+        # upstream's arguments (ptEmb_head.py:732-736).  Template and layer are derived from them at the first engine build.
+        self._mano_assets = None
+        self.mano_assets_source = None
+        self._template_from_assets = False
+        self._auto_mano_layer = None
+        if cfg.get("MANO_ASSETS", None):
+            self._mano_assets = normalise_mano_assets(cfg.get("MANO_ASSETS"))
+            self.mano_assets_source = f"config:{cfg.get('MANO_ASSETS')}"
+        else:
+            found = mano_assets_from_manotorch(self.transformer_center_idx)
+            if found is not None:
+                self._mano_assets, self.mano_assets_source = found, "manotorch"
 
     # ---- configuration of external inputs -------------------------------------------------------------------
     def set_template(self, template_xyz):
@@ -98,7 +132,57 @@ class POEM_Generalized_Head(nn.Module):
         t = torch.as_tensor(template_xyz, dtype=torch.float32).reshape(799, 3)
         self.template = t.to(self.template.device)
         self._template_is_synthetic = False
+        self._template_from_assets, self._own_template = False, None      # the caller's from here on
         self._drop_engines()
+
+    def set_mano_assets(self, arrays_or_path):
+        """The five MANO arrays (``v_template, shapedirs, posedirs, J_regressor, weights``) as a mapping or the path of an
+        ``.npz`` holding them; overrides the ``MANO_ASSETS`` config key and an importable manotorch.  At the next forward the
+        head takes its template from ``ManoLayer.from_arrays(...).zero_pose_template()`` and, with ``PARAMETRIC_OUTPUT``,
+        installs that layer as ``mano_layer`` -- unless the caller has given a template (``set_template``) or a layer
+        (``set_mano_layer`` / ``head.mano_layer = ...``) of their own: those always win and are never overwritten."""
+        self._mano_assets = normalise_mano_assets(arrays_or_path)
+        self.mano_assets_source = f"file:{arrays_or_path}" if isinstance(arrays_or_path, (str, os.PathLike)) else "arrays"
+        if self._template_from_assets and self.template is self._own_template:     # derived from the previous assets: derive again
+            self._template_is_synthetic, self._template_from_assets = True, False
+        if self._auto_mano_layer is not None and self.mano_layer is self._auto_mano_layer:
+            self.mano_layer = None
+        self._auto_mano_layer = None
+        return self
+
+    def _resolve_mano_assets(self, device):
+        """Template and MANO layer from the known assets, on the device of the engine that is about to be built."""
+        if self._mano_assets is None:
+            return
+        need_template = self._template_is_synthetic and self.template is self._own_template
+        need_layer = self.parametric_output and self.mano_layer is None
+        if not (need_template or need_layer):
+            return
+        from .mano import ManoLayer
+        layer = ManoLayer.from_arrays(**self._mano_assets, center_idx=self.transformer_center_idx, device=device)
+        if need_template:
+            self.template = self._own_template = layer.zero_pose_template().to(self.template.device)
+            self._template_is_synthetic, self._template_from_assets = False, True
+            self._drop_engines()
+        if need_layer:
+            self._auto_mano_layer = layer
+            self.set_mano_layer(layer)
+
+    def _ready_template(self, device):
+        """What comes before an engine is built or reused, in this order and from this one place (``_engine_for``): resolve the
+        template and the MANO layer from the assets, refuse the synthetic template after a reference checkpoint, warn about it
+        otherwise."""
+        self._resolve_mano_assets(device)
+        if self._template_is_synthetic and self._reference_checkpoint_loaded:
+            raise RuntimeError("POEM_Generalized_Head: a reference checkpoint was loaded (load_state_dict swallowed "
+                               f"{len(self.ignored_reference_keys)} dead reference tensors) but the hand template is still the "
+                               "synthetic one, so every prediction would be decoded against the wrong mesh.  Give the head the MANO "
+                               "assets -- the MANO_ASSETS config key (an .npz of v_template, shapedirs, posedirs, J_regressor, "
+                               "weights) or set_mano_assets() -- or the zero-pose template itself with set_template()")
+        if self._template_is_synthetic and not getattr(self, "_warned", False):
+            warnings.warn("POEM_Generalized_Head: using the synthetic hand template (MANO assets absent); "
+                          "call set_template() with ManoLayer's zero-pose output for real checkpoints")
+            self._warned = True
 
     def set_mano_layer(self, fn):
         """callable (pose_aa (B,48), betas (B,10)) -> .verts / .joints.  The package's own :class:`~poem_v2_amd.mano.ManoLayer`
@@ -109,13 +193,30 @@ class POEM_Generalized_Head(nn.Module):
         for eng in self._engines.values():
             self._attach_mano(eng)
 
-    def _attach_mano(self, eng):
+    def _mano_to_attach(self, eng):
+        """(table, centre) of the package's own ManoLayer when it can run inside ``eng``'s forward, else (None, 9)."""
         from .mano import ManoLayer
         m = self.mano_layer
-        own = (isinstance(m, ManoLayer) and self.parametric_output and m.th_table.device == eng.device
+        own = (isinstance(m, ManoLayer) and self.parametric_output and _same_device(m.th_table.device, eng.device)
                and not getattr(self, "mano_in_python", False))
-        eng.attach_mano(m.th_table if own else None, m.center_idx if own else 9)
-        return own
+        return (m.th_table, int(m.center_idx)) if own else (None, 9)
+
+    def _attach_mano(self, eng):
+        table, centre = self._mano_to_attach(eng)
+        eng.attach_mano(table, centre)
+        return table is not None
+
+    # ---- strict loading ------------------------------------------------------------------------------------------
+    def _classifier_kw(self):
+        return dict(embed=self.embed_dims, in_channels=self.in_channels, nquery=self.num_query, nblocks=self.transformer.layer_num,
+                    parametric=self.parametric_output, petr=self.PETR_embedding, depth_num=self.depth_num,
+                    pt_feat_dim=self.pt_feat_dim, num_preds=self.num_preds)
+
+    def _note_ignored(self, keys):
+        # (the decoder's own filter has already taken its keys: they are listed with the head's)
+        self.ignored_reference_keys = sorted(keys + ["transformer." + k for k in self.transformer.ignored_reference_keys])
+        # dead reference tensors arrived: a real reference checkpoint, whose template is MANO's (see forward)
+        self._reference_checkpoint_loaded = bool(self.ignored_reference_keys)
 
     def load_reference_state_dict(self, sd):
         """Load a reference checkpoint (full model or head-only); dead tensors are ignored."""
@@ -149,7 +250,11 @@ class POEM_Generalized_Head(nn.Module):
 
     def _apply(self, fn, *a, **k):
         self._plist = None                     # .to() / .cuda() / .float(): the parameters move
-        return super()._apply(fn, *a, **k)
+        own = self._buffers.get("template") is getattr(self, "_own_template", None)
+        out = super()._apply(fn, *a, **k)
+        if own:                                # (the moved copy of the head's own template is still the head's own)
+            self._own_template = self._buffers.get("template")
+        return out
 
     def __delattr__(self, name):
         self._plist = None                     # `del head.x`: a removed submodule's cached _parameters dict must not be read again
@@ -168,6 +273,7 @@ class POEM_Generalized_Head(nn.Module):
         # of 2, the reference's evaluation batch -- gets one engine per stream, so consecutive forwards never share scratch
         # memory and may overlap on the GPU (bench.py small_batch_scope `two_streams`: +7 % at batch 4, nothing at batch <= 2
         # with the default four hardware queues).  Same kernels, same bits.
+        self._ready_template(device)
         if getattr(self, "_plist", None) is None or self._plist_epoch != _TREE_EPOCH[0]:
             mods = list(self.modules())
             self._plist = [m._parameters for m in mods]      # (the module set itself: re-walked when a module tree changed)
@@ -285,11 +391,13 @@ class POEM_Generalized_Head(nn.Module):
         if views.max() > self.max_views:
             self.max_views = int(views.max())
             self._drop_engines()
-        if self._template_is_synthetic and not getattr(self, "_warned", False):
-            warnings.warn("POEM_Generalized_Head: using the synthetic hand template (MANO assets absent); "
-                          "call set_template() with ManoLayer's zero-pose output for real checkpoints")
-            self._warned = True
         eng = self._engine_for(device)
+        if self.parametric_output:
+            # the attached table must be the CURRENT mano_layer's and its centre the current one (`head.mano_layer = other`,
+            # `layer.center_idx = c` after the engine was built): re-attach first, as transformer.py does for its own route
+            table, centre = self._mano_to_attach(eng)
+            if getattr(eng, "_mano", None) is not table or (table is not None and eng._mano_center != centre):
+                eng.attach_mano(table, centre)
         f32 = lambda t: t.to(device=device, dtype=torch.float32).contiguous()   # noqa: E731
         out, pose, betas = eng.head_forward(f32(mlvl_feat), f32(img_metas["cam_intr"]), f32(img_metas["cam_extr"]), views,
                                             f32(reference_joints), (inp_img_w, inp_img_h))

@@ -404,6 +404,7 @@ class Engine:
         """The MANO layer inside the forward (include/poem_hip.h poem_attach_mano); ``table`` = ManoLayer.th_table or None."""
         check(lib().poem_attach_mano(self.handle, None if table is None else table.data_ptr(), int(center_idx)), "poem_attach_mano")
         self._mano = table      # (keeps the caller's table alive while attached)
+        self._mano_center = int(center_idx)
 
     def finalize_parametric(self, verts, joints, reference_joints, out):
         with torch.cuda.device(self.device):

@@ -8,6 +8,8 @@ licence-gated and absent from the reference tree, and manotorch itself is a thir
 the layer takes the five arrays as INPUTS (:meth:`ManoLayer.from_arrays`; on a licensed machine: the fields of the MANO
 pickle) and the arithmetic is restated from the published model -- parity unpinned (csrc/mano.hip).  Tests and the bench
 use :func:`synthetic_mano_assets`.  No CPU fallback."""
+import os
+import warnings
 from collections import namedtuple
 
 import numpy as np
@@ -37,6 +39,64 @@ def synthetic_mano_assets(seed=0):
         w[i, js] = g.dirichlet([4.0, 1.0, 0.5])
     return {"v_template": v.astype(np.float32), "shapedirs": shapedirs.astype(np.float32),
             "posedirs": posedirs.astype(np.float32), "J_regressor": jr.astype(np.float32), "weights": w.astype(np.float32)}
+
+
+ASSET_SHAPES = {"v_template": (NV, 3), "shapedirs": (NV, 3, 10), "posedirs": (NV, 3, 135), "J_regressor": (NJ, NV),
+                "weights": (NV, NJ)}
+
+
+def normalise_mano_assets(arrays_or_path):
+    """The five asset arrays as fp32 numpy arrays of :data:`ASSET_SHAPES`, from a mapping (arrays or tensors; manotorch's
+    buffer layouts -- ``th_v_template`` (1,778,3), ``th_posedirs`` (135,2334) -- are accepted) or the path of an ``.npz``
+    holding them.  Host work only: nothing here touches the device."""
+    src = arrays_or_path
+    if isinstance(src, (str, os.PathLike)):
+        with np.load(os.fspath(src)) as z:
+            src = {k: z[k] for k in z.files}
+    out = {}
+    for k, shp in ASSET_SHAPES.items():
+        if k not in src:
+            raise KeyError(f"MANO assets lack {k!r} (expected {', '.join(ASSET_SHAPES)})")
+        v = src[k]
+        a = np.asarray(v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else v, dtype=np.float32)
+        if k == "posedirs" and a.shape == (135, NV * 3):
+            a = a.T.reshape(NV, 3, 135)
+        if k == "v_template" and a.shape == (1, NV, 3):
+            a = a[0]
+        if a.shape != shp:
+            raise ValueError(f"MANO asset {k}: shape {a.shape} != {shp}")
+        out[k] = np.ascontiguousarray(a)
+    return out
+
+
+def mano_assets_from_manotorch(center_idx=9):
+    """The asset arrays out of ``manotorch.manolayer.ManoLayer`` built with upstream's arguments (ptEmb_head.py:732-736), read
+    from its ``th_*`` buffers -- or None, leaving the caller exactly where it was without manotorch.  A manotorch that cannot
+    be imported is the ordinary case and says nothing.  One that is importable but does not deliver -- its constructor fails (the
+    licence-gated pickle is missing), it lacks one of the five buffers, a buffer has another layout than the one restated here --
+    gives None with a warning that names what went wrong.  Anything else that fails in here is a bug and propagates."""
+    try:
+        from manotorch.manolayer import ManoLayer as _TorchManoLayer
+    except ImportError:
+        return None
+    try:          # third-party constructor: whatever it raises (a missing MANO pickle, typically) is reported, not hidden
+        layer = _TorchManoLayer(joint_rot_mode="axisang", use_pca=False, mano_assets_root="assets/mano_v1_2",
+                                center_idx=center_idx, flat_hand_mean=True)
+    except Exception as e:        # noqa: BLE001
+        warnings.warn(f"manotorch is importable but its ManoLayer could not be built ({type(e).__name__}: {e}); "
+                      "no MANO assets are taken from it")
+        return None
+    found = {k: getattr(layer, "th_" + k, None) for k in ASSET_SHAPES}
+    lacking = [k for k, v in found.items() if v is None]
+    if lacking:
+        warnings.warn("manotorch's ManoLayer lacks the buffers " + ", ".join("th_" + k for k in lacking) +
+                      "; no MANO assets are taken from it")
+        return None
+    try:
+        return normalise_mano_assets(found)
+    except ValueError as e:       # (a buffer of another layout than ASSET_SHAPES / manotorch's two known variants)
+        warnings.warn(f"manotorch's ManoLayer buffers do not have the expected layout ({e}); no MANO assets are taken from it")
+        return None
 
 
 class ManoLayer(torch.nn.Module):

@@ -34,6 +34,11 @@ class PtEmbedMultiviewStereoV2:
         self.img_backbone = HRNet(cfg.get("BACKBONE", None), device=self.device)  # POEM.py:57
         self.ptEmb_head = build_head(cfg.HEAD, data_preset=preset)                # POEM.py:114
         self.num_preds = self.ptEmb_head.num_preds
+        # MANO_ASSETS at the model node (the same .npz path as MODEL.HEAD.MANO_ASSETS) reaches the head unless the head's own node
+        # names some (head.py: template and MANO layer from them)
+        if cfg.get("MANO_ASSETS", None) and not cfg.HEAD.get("MANO_ASSETS", None):
+            self.ptEmb_head.set_mano_assets(cfg.get("MANO_ASSETS"))
+            self.ptEmb_head.mano_assets_source = f"config:{cfg.get('MANO_ASSETS')}"       # (a config key, not a caller's call)
         # confidence-aware DLT (upstream's triangulate_dlt, lib/utils/triangulation.py:111-148): "off" | "threshold" | "weighted"
         self.dlt_confidence = str(cfg.get("DLT_CONFIDENCE", "off")).lower()
         self.dlt_threshold = float(cfg.get("DLT_CONFIDENCE_THRESHOLD", 0.5))
@@ -49,13 +54,18 @@ class PtEmbedMultiviewStereoV2:
         self.loss_metric = LossMetric(cfg)                                        # POEM.py:146 (allocates at its first feed)
 
     # -- weights ----------------------------------------------------------------------------------------------------
-    def load_state_dict(self, sd):
+    def load_state_dict(self, sd, strict=True):
         """Full-model checkpoint in the reference's key names: ``img_backbone.*``, ``feat_delayer.*`` / ``feat_in.*`` /
-        ``uv_delayer.*`` / ``uv_out.*``, ``ptEmb_head.*``.  Returns the keys that were ignored (dead tensors)."""
+        ``uv_delayer.*`` / ``uv_out.*``, ``ptEmb_head.*`` (optionally behind ``module.``, as upstream's ``load_weights`` strips
+        it).  The head takes the strict path of ``nn.Module.load_state_dict``: exactly the reference's dead tensors are
+        swallowed (``weights.is_dead_reference_key``); an unknown ``ptEmb_head.*`` key, a missing live tensor or a live tensor
+        of the wrong shape raises.  Returns the keys that were ignored (dead tensors)."""
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
         ignored = self.img_backbone.load_state_dict(sd, prefix="img_backbone.")
         self.decoders = FeatureDecoders.load_reference_state_dict(sd, self.device)
         head_sd = {k[len("ptEmb_head."):]: v for k, v in sd.items() if k.startswith("ptEmb_head.")}
-        ignored += ["ptEmb_head." + k for k in self.ptEmb_head.load_reference_state_dict(head_sd)]
+        self.ptEmb_head.load_state_dict(head_sd, strict=strict)
+        ignored += ["ptEmb_head." + k for k in self.ptEmb_head.ignored_reference_keys]
         self.ptEmb_head.to(self.device).eval()
         return ignored
 

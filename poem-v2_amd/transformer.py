@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .builder import TRANSFORMER
+from .weights import StrictLoadFilter
 
 
 class _Bag(nn.Module):
@@ -99,6 +100,16 @@ class PtEmbedTRv4(nn.Module):
         self._init_weights()
         self._engine_owner = None   # the head that owns the HIP engine (set by POEM_Generalized_Head)
         self._own_engine = None
+        # strict loading of a reference checkpoint (weights.StrictLoadFilter): the per-block dead tensors -- BERT embeddings,
+        # pooler, position embeddings -- leave load_state_dict's unexpected keys; listed here relative to this module
+        self.ignored_reference_keys = []
+        StrictLoadFilter(self, "transformer.", self._classifier_kw, self._note_ignored)
+
+    def _classifier_kw(self):
+        return dict(embed=self.input_feat_dim, nquery=self.nquery, nblocks=self.layer_num, parametric=self.parametric_output)
+
+    def _note_ignored(self, keys):
+        self.ignored_reference_keys = sorted(keys)
 
     def _init_weights(self):
         # BERT-v4 ``init_weights`` as applied by point_METRO_block to every sub-module (pt_metro_transformer.py:129)

@@ -115,13 +115,24 @@ def load_template(path):
     return torch.as_tensor(np.asarray(t), dtype=torch.float32).reshape(799, 3)
 
 
-def install_template(head, reload, template):
+def head_state_dict(sd):
+    """The head's part of a checkpoint -- full model (``ptEmb_head.*``, optionally behind ``module.`` as upstream's ``load_weights``
+    strips it) or head only -- for a plain ``head.load_state_dict(..., strict=True)``."""
+    sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
+    if any(k.startswith("ptEmb_head.") for k in sd):
+        sd = {k[len("ptEmb_head."):]: v for k, v in sd.items() if k.startswith("ptEmb_head.")}
+    return sd
+
+
+def install_template(head, reload, template, mano_assets=None):
     """Which hand template the head runs with, and a word for the result record.  A seeded synthetic template is only
-    right for seeded synthetic weights: with ``--reload`` the template must come from ``--template``; otherwise the head's
-    own "synthetic template" warning is left armed and the record says so."""
+    right for seeded synthetic weights: with ``--reload`` the template must come from ``--template`` or ``--mano-assets`` (the head
+    derives it from the assets itself; it refuses to run a reference checkpoint on the synthetic one)."""
     if template:
         head.set_template(load_template(template))
         return f"file:{template}"
+    if mano_assets:
+        return f"mano-assets:{mano_assets}"
     if reload:
         return "synthetic (NO --template given with --reload: metrics are not meaningful for a real checkpoint)"
     head.set_template(pk.inputs.synthetic_template(1234))
@@ -129,7 +140,7 @@ def install_template(head, reload, template):
 
 
 def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, batch_size=2, seed=0, verbose=True,
-             pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None):
+             pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, mano_assets=None):
     """``draw``: a ``DrawingHandCallback`` (rank 0, ``--draw --faces``) called with every batch.  This scope has no images: the panels
     show the meshes and skeletons over mid-grey views."""
     rank, _, world = pdist.env_world()
@@ -138,20 +149,22 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
                          "behind the heat-map stage)")
     head_node = pk.CN(cfg["MODEL"]["HEAD"])
     head_node["MAX_VIEWS"] = max(10, int(view_range[1]))
+    if mano_assets:
+        head_node["MANO_ASSETS"] = mano_assets       # template and (medium_MANO) the MANO layer come from the assets, in the head
     head = pk.build_head(head_node, data_preset=pk.CN({}))
     embed = head.embed_dims
     if reload:
         sd = torch.load(reload, map_location="cpu")
         sd = sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd
-        ignored = head.load_reference_state_dict(sd)
+        head.load_state_dict(head_state_dict(sd), strict=True)
         if verbose and rank == 0:
-            print(f"reloaded {reload}: {len(ignored)} dead tensors ignored")
+            print(f"reloaded {reload}: {len(head.ignored_reference_keys)} dead tensors ignored")
     else:
         head.load_state_dict(pk.weights.seeded_state_dict(embed, seed=0, parametric=head.parametric_output), strict=False)
-    template_source = install_template(head, reload, template)
-    if head.parametric_output:
-        raise SystemExit("medium_MANO needs a MANO layer (licence-gated assets): call head.set_mano_layer(fn) from "
-                         "Python; this script evaluates the non-parametric categories")
+    template_source = install_template(head, reload, template, mano_assets)
+    if head.parametric_output and not mano_assets:
+        raise SystemExit("medium_MANO needs a MANO layer (licence-gated assets): pass --mano-assets FILE.npz (v_template, shapedirs, "
+                         "posedirs, J_regressor, weights), or call head.set_mano_layer(fn) from Python")
     head = head.to(device).eval()
     # --pyramid: start one stage earlier, at the backbone's multi-level features (lib/models/POEM.py:264-270 upstream):
     # feat_decode gives the head's mlvl_feat, heatmap_stage the per-view 2-D joints that are triangulated
@@ -238,7 +251,8 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
 
 
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
-                    n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None):
+                    n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
+                    mano_assets=None):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -267,19 +281,25 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
                   "DLT_CONFIDENCE": dlt_confidence, "DLT_CONFIDENCE_THRESHOLD": dlt_threshold}
     if losses is not None:
         model_node["LOSS"] = loss_node(cfg)
+    if mano_assets:
+        model_node["MANO_ASSETS"] = mano_assets
     model = pk.build_model(pk.CN(model_node))
     if losses is not None:
         model.set_j_regressor(losses)
     if reload:
         sd = torch.load(reload, map_location="cpu")
         model.load_state_dict(sd.get("state_dict", sd.get("model", sd)) if isinstance(sd, dict) else sd)
-        template_source = install_template(model.ptEmb_head, reload, template)
+        template_source = install_template(model.ptEmb_head, reload, template, mano_assets)
     else:
-        template_source = f"file:{template}" if template else "synthetic(seed=1234)"
+        template_source = f"file:{template}" if template else f"mano-assets:{mano_assets}" if mano_assets else "synthetic(seed=1234)"
         from poem_v2_amd.backbone import seeded_hrnet_state_dict
         model.load_parts(seeded_hrnet_state_dict(0), pk.weights.seeded_decoder_state_dict(0),
-                         pk.weights.seeded_state_dict(model.ptEmb_head.embed_dims, seed=0),
-                         template=load_template(template) if template else pk.inputs.synthetic_template(1234))
+                         pk.weights.seeded_state_dict(model.ptEmb_head.embed_dims, seed=0,
+                                                      parametric=model.ptEmb_head.parametric_output),
+                         template=load_template(template) if template else None if mano_assets
+                         else pk.inputs.synthetic_template(1234))
+    if model.ptEmb_head.parametric_output and not mano_assets:
+        raise SystemExit("medium_MANO needs a MANO layer (licence-gated assets): pass --mano-assets FILE.npz")
     mpvpe, mpjpe = MeanEPE("verts", device=device), MeanEPE("joints", device=device)
     n, t0, frames, steps, t_draw = 0, None, [], [0], [0.0]
 
@@ -331,6 +351,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
 def main(args):
     view_range = [args.view_min, args.view_max]
     check_losses_args(args)
+    mano_assets = getattr(args, "mano_assets", None)          # (absent from a build_parser() namespace)
     if args.cfg and os.path.exists(args.cfg):
         with open(args.cfg, "r") as f:
             cfg = yaml.load(f, Loader=yaml.FullLoader)
@@ -372,11 +393,11 @@ def main(args):
         res = evaluate_shards(cfg, view_range, args.model, device, args.shards, args.dataset, reload=args.reload,
                               epoch_size=args.epoch_size, batch_size=args.batch_size, template=args.template,
                               dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw,
-                              losses=j_regressor)
+                              losses=j_regressor, mano_assets=mano_assets)
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
-                       dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw)
+                       dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw, mano_assets=mano_assets)
     if rank == 0:
         exp_id = f"{args.dataset}_view_{view_range[0]}_{view_range[1]}_{args.model}"
         if args.model == "huge":
@@ -408,7 +429,7 @@ def build_parser():
                              "shards are written there when absent): tar records -> device transform -> model -> metrics")
     parser.add_argument("--template", type=str, default=None, metavar="FILE",
                         help="(799,3) zero-pose hand template (.npy / .pt; ManoLayer's zero-pose joints + vertices, centred at "
-                             "joint 9).  Required for meaningful metrics with --reload; synthetic otherwise (this build).")
+                             "joint 9).  With --reload either this or --mano-assets is required; synthetic otherwise (this build).")
     parser.add_argument("--dlt-confidence", choices=("off", "threshold", "weighted"), default="off",
                         help="Discount views by their heat-map peak in the DLT of the reference joints (model key DLT_CONFIDENCE; "
                              "threshold = upstream's triangulate_dlt).  Needs --pyramid or --shards.")
@@ -427,5 +448,15 @@ def build_parser():
     return parser
 
 
+def build_cli():
+    """``build_parser()`` -- the argument surface the host tests pin key by key -- plus the arguments added since."""
+    parser = build_parser()
+    parser.add_argument("--mano-assets", type=str, default=None, metavar="FILE.npz",
+                        help="MANO's five arrays (v_template, shapedirs, posedirs, J_regressor, weights; on a licensed machine: the fields "
+                             "of MANO_RIGHT.pkl).  The head takes its zero-pose template and, for medium_MANO, its MANO layer from them: "
+                             "--reload needs no --template, and medium_MANO runs (head config key MANO_ASSETS).")
+    return parser
+
+
 if __name__ == "__main__":
-    main(build_parser().parse_args())
+    main(build_cli().parse_args())
