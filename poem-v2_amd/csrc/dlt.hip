@@ -6,42 +6,35 @@
 //   x   = right singular vector of A for the smallest singular value;  X = x[:3] / (x[3] + 1e-7)
 // The reference calls torch.linalg.svd on every (2N x 4) matrix; here the 4x4 normal matrix A^T A is accumulated in
 // fp64 and its smallest eigenvector found with cyclic Jacobi rotations in fp64 (same subspace; measured closer to the
-// fp64 SVD than the reference's fp32 SVD is).  One thread per (sample, joint): the whole stage is ~700 threads.
+// fp64 SVD than the reference's fp32 SVD is).  dlt_kernel: one thread per (sample, joint), the whole stage is ~700 threads.
 #include "common.h"
 
-__device__ inline void dlt_invert4x4(const float* __restrict__ m, double (&o)[4][4]) {
-  double a[4][8];
-  for (int i = 0; i < 4; ++i)
-    for (int j = 0; j < 4; ++j) { a[i][j] = (double)m[i * 4 + j]; a[i][4 + j] = (i == j) ? 1.0 : 0.0; }
-  for (int c = 0; c < 4; ++c) {
-    int piv = c;
-    double best = fabs(a[c][c]);
-    for (int i = c + 1; i < 4; ++i) if (fabs(a[i][c]) > best) { best = fabs(a[i][c]); piv = i; }
-    if (piv != c) for (int j = 0; j < 8; ++j) { const double t = a[c][j]; a[c][j] = a[piv][j]; a[piv][j] = t; }
-    const double inv = 1.0 / a[c][c];
-    for (int j = 0; j < 8; ++j) a[c][j] *= inv;
-    for (int i = 0; i < 4; ++i) if (i != c) {
-      const double f = a[i][c];
-      for (int j = 0; j < 8; ++j) a[i][j] -= f * a[c][j];
-    }
-  }
-  for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) o[i][j] = a[i][4 + j];
-}
+#define DLT_MODE_THRESHOLD 1
+#define DLT_MODE_WEIGHTED 2
 
-__global__ __launch_bounds__(64) void dlt_kernel(const float* __restrict__ uv, const float* __restrict__ intr,
-                                                 const float* __restrict__ mat, const int* __restrict__ offs,
-                                                 float* __restrict__ out, int B, int J, int invert) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= B * J) return;
-  const int b = t / J, j = t % J;
-  const int v0 = offs[b], v1 = offs[b + 1];
+// Joint j of a sample over its views v0..v1 -> o[0..2]; returns the number of views that took part.  CONF = false is the plain
+// solve (conf, mode and thr are not read).  CONF = true, the confidence-aware form (below): a view takes part when its
+// confidence is above thr (mode 1), or both its rows are scaled by its confidence (mode 2).  Everything else is one
+// arithmetic -- M and the rows in fp32, normal matrix and Jacobi in fp64, the sign, the +1e-7 of :43 -- so that confidence 1
+// everywhere (mode 2) or a threshold of 0 with positive confidences (mode 1) gives the plain solve's bits.
+template <bool CONF>
+__device__ __forceinline__ int dlt_solve(const float* __restrict__ uv, const float* __restrict__ conf,
+                                         const float* __restrict__ intr, const float* __restrict__ mat, int v0, int v1, int J,
+                                         int j, int invert, int mode, double thr, float* __restrict__ o) {
+  int used = 0;
   double G[4][4] = {};
   for (int v = v0; v < v1; ++v) {
+    double cf = 1.0;
+    if constexpr (CONF) {
+      cf = (double)conf[(size_t)v * J + j];
+      if (mode == DLT_MODE_THRESHOLD && !(cf > thr)) continue;                   // :135
+    }
+    ++used;
     float T[3][4];
     if (invert) {
-      double Ti[4][4];
-      dlt_invert4x4(mat + (size_t)v * 16, Ti);
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = (float)Ti[r][c];
+      double Ti[16];
+      invert4x4(mat + (size_t)v * 16, Ti);                                        // (common.h)
+      for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = (float)Ti[r * 4 + c];
     } else {
       for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = mat[(size_t)v * 16 + r * 4 + c];
     }
@@ -52,8 +45,16 @@ __global__ __launch_bounds__(64) void dlt_kernel(const float* __restrict__ uv, c
     const float u = uv[((size_t)v * J + j) * 2], w = uv[((size_t)v * J + j) * 2 + 1];
     float a0[4], a1[4];
     for (int c = 0; c < 4; ++c) { a0[c] = u * M[2][c] - M[0][c]; a1[c] = w * M[2][c] - M[1][c]; }
-    for (int r = 0; r < 4; ++r)
-      for (int c = r; c < 4; ++c) G[r][c] += (double)a0[r] * (double)a0[c] + (double)a1[r] * (double)a1[c];
+    if constexpr (CONF) {
+      const double sc = mode == DLT_MODE_WEIGHTED ? cf : 1.0;
+      double d0[4], d1[4];
+      for (int c = 0; c < 4; ++c) { d0[c] = (double)a0[c] * sc; d1[c] = (double)a1[c] * sc; }
+      for (int r = 0; r < 4; ++r)
+        for (int c = r; c < 4; ++c) G[r][c] += d0[r] * d0[c] + d1[r] * d1[c];
+    } else {
+      for (int r = 0; r < 4; ++r)
+        for (int c = r; c < 4; ++c) G[r][c] += (double)a0[r] * (double)a0[c] + (double)a1[r] * (double)a1[c];
+    }
   }
   for (int r = 1; r < 4; ++r) for (int c = 0; c < r; ++c) G[r][c] = G[c][r];
   // cyclic Jacobi: G <- R^T G R, V <- V R
@@ -76,11 +77,21 @@ __global__ __launch_bounds__(64) void dlt_kernel(const float* __restrict__ uv, c
   int m = 0;
   for (int k = 1; k < 4; ++k) if (G[k][k] < G[m][m]) m = k;
   double x[4] = {V[0][m], V[1][m], V[2][m], V[3][m]};
-  if (x[3] < 0) { x[0] = -x[0]; x[1] = -x[1]; x[2] = -x[2]; x[3] = -x[3]; }      // the sign of a singular vector is free
-  const double den = x[3] + 1e-7;                                                // triangulation.py:43
-  out[(size_t)t * 3 + 0] = (float)(x[0] / den);
-  out[(size_t)t * 3 + 1] = (float)(x[1] / den);
-  out[(size_t)t * 3 + 2] = (float)(x[2] / den);
+  if (x[3] < 0) { x[0] = -x[0]; x[1] = -x[1]; x[2] = -x[2]; x[3] = -x[3]; }        // the sign of a singular vector is free
+  const double den = x[3] + 1e-7;                                                  // triangulation.py:43
+  o[0] = (float)(x[0] / den);
+  o[1] = (float)(x[1] / den);
+  o[2] = (float)(x[2] / den);
+  return used;
+}
+
+__global__ __launch_bounds__(64) void dlt_kernel(const float* __restrict__ uv, const float* __restrict__ intr,
+                                                 const float* __restrict__ mat, const int* __restrict__ offs,
+                                                 float* __restrict__ out, int B, int J, int invert) {
+  const int t = blockIdx.x * blockDim.x + threadIdx.x;
+  if (t >= B * J) return;
+  const int b = t / J, j = t % J;
+  dlt_solve<false>(uv, nullptr, intr, mat, offs[b], offs[b + 1], J, j, invert, 0, 0.0, out + (size_t)t * 3);
 }
 
 extern "C" hipError_t poem_launch_dlt(const float* uv, const float* intr, const float* mat, const int* offs, float* out,
@@ -92,7 +103,7 @@ extern "C" hipError_t poem_launch_dlt(const float* uv, const float* intr, const 
 
 // ---------------------------------------------------------------------------------------------------------
 // Confidence-aware form of the same solve.  Replaces lib/utils/triangulation.py:111-148 (triangulate_dlt) and the
-// per-sample loop a caller would put around it; dlt_kernel above is untouched and stays the default route.
+// per-sample loop a caller would put around it: dlt_solve<true>; dlt_kernel stays the default route.
 //   mode 1 (threshold), triangulation.py:133-147 as it runs: per joint, in order, a camera is selected when
 //     conf > thr; while at most one camera is selected and thr > 0, thr -= 0.05 (fp64, :139).  `confi_thres` is the
 //     function's own argument, so a lowered threshold is what the FOLLOWING joints of that sample start from.  That is
@@ -101,12 +112,7 @@ extern "C" hipError_t poem_launch_dlt(const float* uv, const float* intr, const 
 //     the selected cameras.  No workspace, no second launch, nothing read back by the host.
 //   mode 2 (weighted): both rows of view n are scaled by conf[n][j] (fp64, after the fp32 row is formed); no view is
 //     dropped.  (Upstream has no weighted form; this is the usual confidence-weighted least squares.)
-// Everything else is dlt_kernel's arithmetic statement for statement -- M and the rows in fp32, normal matrix and Jacobi
-// in fp64, the sign, the +1e-7 of :43 -- so that confidence 1 everywhere (mode 2) or a threshold of 0 with positive
-// confidences (mode 1) gives dlt_kernel's bits.  One block per sample, thread j -> joint j (+64, ...).
-#define DLT_MODE_THRESHOLD 1
-#define DLT_MODE_WEIGHTED 2
-
+// One block per sample, thread j -> joint j (+64, ...).
 __global__ __launch_bounds__(64) void dlt_conf_kernel(const float* __restrict__ uv, const float* __restrict__ conf,
                                                       const float* __restrict__ intr, const float* __restrict__ mat,
                                                       const int* __restrict__ offs, float* __restrict__ out,
@@ -132,60 +138,8 @@ __global__ __launch_bounds__(64) void dlt_conf_kernel(const float* __restrict__ 
   }
   for (int j = threadIdx.x; j < J; j += blockDim.x) {
     const size_t t = (size_t)b * J + j;
-    const double thr = mode == DLT_MODE_THRESHOLD ? thr_of[j] : 0.0;
-    int used = 0;
-    double G[4][4] = {};
-    for (int v = v0; v < v1; ++v) {
-      const double cf = (double)conf[(size_t)v * J + j];
-      if (mode == DLT_MODE_THRESHOLD && !(cf > thr)) continue;                   // :135
-      ++used;
-      float T[3][4];
-      if (invert) {
-        double Ti[4][4];
-        dlt_invert4x4(mat + (size_t)v * 16, Ti);
-        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = (float)Ti[r][c];
-      } else {
-        for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = mat[(size_t)v * 16 + r * 4 + c];
-      }
-      const float* K = intr + (size_t)v * 9;
-      float M[3][4];
-      for (int r = 0; r < 3; ++r)
-        for (int c = 0; c < 4; ++c) M[r][c] = fmaf(K[r * 3 + 2], T[2][c], fmaf(K[r * 3 + 1], T[1][c], K[r * 3] * T[0][c]));
-      const float u = uv[((size_t)v * J + j) * 2], w = uv[((size_t)v * J + j) * 2 + 1];
-      float a0[4], a1[4];
-      for (int c = 0; c < 4; ++c) { a0[c] = u * M[2][c] - M[0][c]; a1[c] = w * M[2][c] - M[1][c]; }
-      const double sc = mode == DLT_MODE_WEIGHTED ? cf : 1.0;
-      double d0[4], d1[4];
-      for (int c = 0; c < 4; ++c) { d0[c] = (double)a0[c] * sc; d1[c] = (double)a1[c] * sc; }
-      for (int r = 0; r < 4; ++r)
-        for (int c = r; c < 4; ++c) G[r][c] += d0[r] * d0[c] + d1[r] * d1[c];
-    }
-    for (int r = 1; r < 4; ++r) for (int c = 0; c < r; ++c) G[r][c] = G[c][r];
-    // cyclic Jacobi: G <- R^T G R, V <- V R
-    double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
-    for (int sweep = 0; sweep < 12; ++sweep) {
-      double off = 0.0, diag = 0.0;
-      for (int r = 0; r < 4; ++r) { diag += G[r][r] * G[r][r]; for (int c = r + 1; c < 4; ++c) off += G[r][c] * G[r][c]; }
-      if (off <= 1e-40 * diag) break;
-      for (int p = 0; p < 3; ++p)
-        for (int q = p + 1; q < 4; ++q) {
-          if (G[p][q] == 0.0) continue;
-          const double theta = (G[q][q] - G[p][p]) / (2.0 * G[p][q]);
-          const double tt = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
-          const double c = 1.0 / sqrt(tt * tt + 1.0), s = tt * c;
-          for (int k = 0; k < 4; ++k) { const double gkp = G[k][p], gkq = G[k][q]; G[k][p] = c * gkp - s * gkq; G[k][q] = s * gkp + c * gkq; }
-          for (int k = 0; k < 4; ++k) { const double gpk = G[p][k], gqk = G[q][k]; G[p][k] = c * gpk - s * gqk; G[q][k] = s * gpk + c * gqk; }
-          for (int k = 0; k < 4; ++k) { const double vkp = V[k][p], vkq = V[k][q]; V[k][p] = c * vkp - s * vkq; V[k][q] = s * vkp + c * vkq; }
-        }
-    }
-    int m = 0;
-    for (int k = 1; k < 4; ++k) if (G[k][k] < G[m][m]) m = k;
-    double x[4] = {V[0][m], V[1][m], V[2][m], V[3][m]};
-    if (x[3] < 0) { x[0] = -x[0]; x[1] = -x[1]; x[2] = -x[2]; x[3] = -x[3]; }    // the sign of a singular vector is free
-    const double den = x[3] + 1e-7;                                              // triangulation.py:43
-    out[t * 3 + 0] = (float)(x[0] / den);
-    out[t * 3 + 1] = (float)(x[1] / den);
-    out[t * 3 + 2] = (float)(x[2] / den);
+    const int used = dlt_solve<true>(uv, conf, intr, mat, v0, v1, J, j, invert, mode, mode == DLT_MODE_THRESHOLD ? thr_of[j] : 0.0,
+                                     out + t * 3);
     if (sel_count) sel_count[t] = used;
   }
 }

@@ -223,6 +223,50 @@ def test_hip_sample_alone_equals_sample_in_ragged_batch(mode):
             assert torch.equal(one[0], full[b]) and torch.equal(n1[0], count[b])
 
 
+def _j70_inputs():
+    """70 joints (more than one 64-thread block of dlt_kernel, more than one stride of dlt_conf_kernel's joint loop) of 3 samples
+    with 2 / 3 / 4 views: the synthetic batch's cameras, points within 8 cm of each sample's hand, 1.5 px of noise, confidences
+    in (0.05, 1)."""
+    import poem_v2_amd as pk
+    views = [2, 3, 4]
+    b = pk.inputs.synthetic_batch(views, seed=70)
+    K, E = b["img_metas"]["cam_intr"], b["img_metas"]["cam_extr"]
+    T = torch.linalg.inv(E)
+    g = torch.Generator().manual_seed(170)
+    X = b["reference_joints"].mean(1, keepdim=True) + 0.08 * (torch.rand(len(views), 70, 3, generator=g) * 2 - 1)
+    Xv = X[torch.repeat_interleave(torch.arange(len(views)), torch.tensor(views))]
+    pc = (T[:, None, :3, :3] @ Xv[..., None]).squeeze(-1) + T[:, None, :3, 3]
+    q = (K[:, None] @ pc[..., None]).squeeze(-1)
+    uv = q[..., :2] / q[..., 2:] + 1.5 * torch.randn(sum(views), 70, 2, generator=g)
+    conf = 0.05 + 0.95 * torch.rand(sum(views), 70, generator=g)
+    return views, [t.contiguous().to(DEV) for t in (uv, conf, K, E, T)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("invert", [True, False])
+def test_hip_one_solve_behind_both_kernels_at_70_joints(invert):
+    """dlt_kernel and dlt_conf_kernel run one solve: at J = 70 the plain route equals the weighted route with confidence 1 and the
+    threshold route with threshold 0 bit for bit, and on every route a sample alone equals the same sample in the ragged batch."""
+    import poem_v2_amd as pk
+    views, (uv, cf, K, E, T) = _j70_inputs()
+    mat = E if invert else T
+    tri = pk.triangulation.triangulate_reference_joints
+    plain = tri(uv, K, mat, views, invert=invert)
+    assert plain.shape == (3, 70, 3) and bool(torch.isfinite(plain).all())
+    assert torch.equal(tri(uv, K, mat, views, invert=invert, conf=torch.ones_like(cf), mode="weighted"), plain)
+    assert torch.equal(tri(uv, K, mat, views, invert=invert, conf=cf, mode="threshold", threshold=0.0), plain)
+    offs = np.concatenate([[0], np.cumsum(views)])
+    for mode in (None, "threshold", "weighted"):
+        kw = dict(invert=invert) if mode is None else dict(invert=invert, mode=mode, threshold=0.5, return_count=True)
+        full = tri(uv, K, mat, views, conf=cf, **kw)
+        for b, (s, e) in enumerate(zip(offs[:-1], offs[1:])):
+            one = tri(uv[s:e], K[s:e], mat[s:e], [views[b]], conf=cf[s:e], **kw)
+            if mode is None:
+                assert torch.equal(one[0], full[b]), b
+            else:                                                          # (joints, camera counts)
+                assert torch.equal(one[0][0], full[0][b]) and torch.equal(one[1][0], full[1][b]), (mode, b)
+
+
 @pytest.mark.gpu
 def test_hip_feature_recovers_occluded_views():
     """Case (b) on the device: the plain DLT is more than 1 cm from the true joints on every joint, threshold mode is back on

@@ -81,6 +81,46 @@ def test_knn_k_ties_nan_and_small_counts(K):
     assert torch.equal(idx[..., :20].cpu().long(), po.knn_indices(qx, s, 20)) and bool((idx[..., 20:] == -7).all())
 
 
+def _knn_k_rows64(qx, sx, K, fma):
+    """poem_knn_k at row stride 64 into rows pre-filled with -7 (any K: never the K = 32, ld = 32 shortcut into the narrow kernel)."""
+    B, NQ, NS = qx.shape[0], qx.shape[1], sx.shape[1]
+    idx = torch.full((B, NQ, 64), -7, dtype=torch.int32, device=DEV)
+    qd, sd = qx.to(DEV), sx.to(DEV)                                                      # (kept alive across the launch)
+    hip.check(hip.lib().poem_knn_k(hip.ptr(qd), hip.ptr(sd), idx.data_ptr(), B, NQ, NS, K, 64, int(fma), hip.stream()))
+    torch.cuda.synchronize()
+    return idx.cpu().long()
+
+
+def _wide_sources(case):
+    g = torch.Generator().manual_seed(len(case))
+    qx = torch.rand(2, 70, 3, generator=g) * 2 - 1
+    if case == "same300":                               # every distance of a query equal: the fall-back rounds
+        return qx, torch.zeros(2, 300, 3)
+    return qx, torch.rand(2, {"ns130": 130, "ns500": 500}[case], 3, generator=g) * 2 - 1
+
+
+@pytest.mark.parametrize("fma", [False, True])
+@pytest.mark.parametrize("case", ["ns130", "ns500", "same300"])
+def test_wide_body_at_k32_equals_the_narrow_kernel(case, fma):
+    """One query routine behind both kernels: knn_kernel_k at K = 32 (row stride 64) writes what knn_kernel writes, which is the
+    oracle's order; columns 32..63 are not touched.  NS = 130: two 128-candidate pairs, the second all padding but two."""
+    qx, sx = _wide_sources(case)
+    got = _knn_k_rows64(qx, sx, 32, fma)
+    narrow = hip.knn(qx.to(DEV), sx.to(DEV), fma=fma, k=32).cpu().long()
+    assert torch.equal(got[..., :32], narrow) and torch.equal(narrow, po.knn_indices(qx, sx, 32, fma))
+    assert bool((got[..., 32:] == -7).all())
+
+
+@pytest.mark.parametrize("fma", [False, True])
+def test_wide_body_at_k1_and_k_equal_to_ns(fma):
+    qx, sx = _wide_sources("ns500")
+    got = _knn_k_rows64(qx, sx, 1, fma)
+    assert torch.equal(got[..., :1], po.knn_indices(qx, sx, 1, fma)) and bool((got[..., 1:] == -7).all())
+    sx = sx[:, :40].contiguous()                        # K = NS = 40: every source, in order
+    got = _knn_k_rows64(qx, sx, 40, fma)
+    assert torch.equal(got[..., :40], po.knn_indices(qx, sx, 40, fma)) and bool((got[..., 40:] == -7).all())
+
+
 # ---- 2. vector attention op ------------------------------------------------------------------------------------------------
 def _va_case(C, K, seed, B=2, Q=101, NS=300):
     g = torch.Generator().manual_seed(seed)
