@@ -403,6 +403,41 @@ int poem_pack_conv3x3(const float* w_oihw, int cout, int cin, void* packed, void
 int poem_conv3x3(const float* in_padded, const void* w_packed, const float* scale, const float* shift,
                  const float* residual, float* out, int views, int cin, int cout, int h, int w, int stride, int relu,
                  int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset, void* stream);
+/* The HRNet-W40 backbone on the same kernels (lib/models/backbones/hrnet.py upstream).  A "map" below
+ * is a (views, c, h, w) tensor given by a pointer and (view_stride, ch_stride, row_stride, offset) in floats: element (n,c,y,x)
+ * is p[n*view_stride + c*ch_stride + y*row_stride + x + offset] -- a plain tensor (c*h*w, h*w, w, 0) or the interior of a
+ * zero-bordered one (c*(h+2)*(w+2), (h+2)*(w+2), w+2, w+3).  A map must stay inside its own channel plane
+ * ((h-1)*row_stride + w-1 + offset < ch_stride): POEM_E_ARG otherwise.
+ * poem_conv3x3_ex: poem_conv3x3 whose residual is a map of its own and, with res_before_act != 0, is added BEFORE the
+ *   activation: y = relu(conv(in)*scale + shift + residual), a BasicBlock (hrnet.py BasicBlock.forward).  With res_before_act
+ *   == 0 and a plain residual the result is poem_conv3x3's, bit for bit.  Same kernels and routing as poem_conv3x3 (direct,
+ *   LDS-staged 32- and 16-row tiles; stride 2 on the direct kernel).  POEM_E_ARG: null pointers, cin % 8; POEM_E_UNSUPPORTED:
+ *   stride other than 1|2, (h/stride)*(w/stride) % 32, a bordered input view of 2 GiB or more.
+ * poem_pack_conv1x1 / poem_conv1x1: 1x1 convolution, weights (cout, cin) row-major packed once (poem_conv1x1_packed_bytes
+ *   bytes; cin % 8 == 0): out = act(sum_ci W[co][ci]*in[ci] + shift[co] + residual) with in, residual (optional, before the
+ *   activation) and out each a map; shift (cout floats) may be null; relu 0|1.  Any cout; (h*w) % 32 == 0.  POEM_E_ARG: null
+ *   pointers, cin % 8, a map outside its plane; POEM_E_UNSUPPORTED: (h*w) % 32, an input view (cin*in_ch_stride floats) of
+ *   2 GiB or more.
+ * poem_hrnet_fuse: the fuse sum of a HighResolutionModule (hrnet.py:226-233): out = relu(((t0 + t1) + t2) + t3) over 2..4
+ *   terms added in that order; term k is a map read at (y >> shift, x >> shift), shift 0..3 -- shift > 0 is
+ *   nn.Upsample(mode="nearest") of a lower-resolution map, never materialised.  ReLU as torch's (NaN propagates). */
+typedef struct poem_fuse_term {
+  const float* data;
+  int64_t view_stride;
+  int32_t ch_stride, row_stride, offset, shift;
+} poem_fuse_term_t;
+int poem_conv3x3_ex(const float* in_padded, const void* w_packed, const float* scale, const float* shift, const float* residual,
+                    int64_t res_view_stride, int res_ch_stride, int res_row_stride, int res_offset, int res_before_act, float* out,
+                    int views, int cin, int cout, int h, int w, int stride, int relu, int64_t out_view_stride, int out_ch_stride,
+                    int out_row_stride, int out_offset, void* stream);
+size_t poem_conv1x1_packed_bytes(int cout, int cin);
+int poem_pack_conv1x1(const float* w_oi, int cout, int cin, void* packed, void* stream);
+int poem_conv1x1(const float* in, int64_t in_view_stride, int in_ch_stride, int in_row_stride, int in_offset, const void* w_packed,
+                 const float* shift, const float* residual, int64_t res_view_stride, int res_ch_stride, int res_row_stride,
+                 int res_offset, float* out, int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset,
+                 int views, int cin, int cout, int h, int w, int relu, void* stream);
+int poem_hrnet_fuse(const poem_fuse_term_t* terms, int nterms, float* out, int64_t out_view_stride, int out_ch_stride,
+                    int out_row_stride, int out_offset, int views, int channels, int h, int w, void* stream);
 int poem_upsample2_concat_pad(const float* a, int ca, const float* b, int cb, float* out, int views, int h, int w, int pad,
                               void* stream);
 /* A stride-2 ConvBlock of feat_decode (POEM.py:183-189: padding 1, stride 2) straight from the UNBORDERED input

@@ -100,9 +100,27 @@ struct Conv3Args {
   const float* head_b;
   float* hmap;
   int J;
+  // poem_conv3x3_ex (the EX instantiations): the residual addressed as `out` is -- it may be the interior of a zero-bordered
+  // buffer -- and, with res_pre, added BEFORE the activation (a BasicBlock: relu(conv * scale + shift + x))
+  int res_pre;
+  long res_ns;
+  int res_cs, res_rs, res_off;
 };
 
-template <int CT, int PT>
+// epilogue tail of the EX instantiations: activation and residual in either order, the residual by its own strides
+__device__ __forceinline__ float conv3_ex_tail(const Conv3Args& A, int n, int co, int oy, int ox, float v) {
+  const float r = A.res ? A.res[(size_t)n * A.res_ns + (size_t)co * A.res_cs + oy * A.res_rs + ox + A.res_off] : 0.f;
+  if (A.res_pre) {
+    if (A.res) v += r;
+    if (A.relu) v = relu_nan(v);
+  } else {
+    if (A.relu) v = fmaxf(v, 0.f);
+    if (A.res) v += r;
+  }
+  return v;
+}
+
+template <int CT, int PT, bool EX = false>
 __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args A) {
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
   const int Ho = A.H / A.stride, Wo = A.W / A.stride, Hp = A.H + 2, Wp = A.W + 2;
@@ -182,8 +200,11 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args A) {
 #pragma unroll
         for (int p = 0; p < PT; ++p) {
           float v = fmaf(acc[c][p][4 * g + e], (&sc.x)[e], (&sh.x)[e]);
-          if (A.relu) v = fmaxf(v, 0.f);
-          if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + py[p] * Wo + px[p]];
+          if constexpr (EX) v = conv3_ex_tail(A, n, co, py[p], px[p], v);
+          else {
+            if (A.relu) v = fmaxf(v, 0.f);
+            if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + py[p] * Wo + px[p]];
+          }
           A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + py[p] * A.out_rs + px[p] + A.out_off] = v;
         }
       }
@@ -419,7 +440,7 @@ struct Conv3RowStager {
 // conv3x3_lds16_kernel -- tap t + 1's weight fragments and operands requested before tap t's MFMAs, the next chunk's staging
 // loads one float per tap behind them.  Left to the compiler the chunk began with the burst of 28 staging gathers and tap 0's
 // weights queued behind it (vmcnt retires in order): every chunk of every wave waited an L2 round trip at the barrier's far side.
-template <int CT, bool UPCAT, bool PIN = false>
+template <int CT, bool UPCAT, bool PIN = false, bool EX = false>
 __global__ __launch_bounds__(512) void conv3x3_lds_kernel(Conv3Args A) {
   extern __shared__ __attribute__((aligned(16))) float tile[];      // 2 x 8 x trows x Wp
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 31, h = lane >> 5;
@@ -531,8 +552,11 @@ __global__ __launch_bounds__(512) void conv3x3_lds_kernel(Conv3Args A) {
         const int co = cbase + 8 * g + e;
         if (co >= A.Cout) continue;
         float v = fmaf(acc[c][4 * g + e], (&sc.x)[e], (&sh.x)[e]);
-        if (A.relu) v = fmaxf(v, 0.f);
-        if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + px];
+        if constexpr (EX) v = conv3_ex_tail(A, n, co, oy, px, v);
+        else {
+          if (A.relu) v = fmaxf(v, 0.f);
+          if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + px];
+        }
         A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + px + A.out_off] = v;
       }
     }
@@ -546,7 +570,7 @@ __global__ __launch_bounds__(512) void conv3x3_lds_kernel(Conv3Args A) {
 // to a stride == 16 mod 32 floats so that the two channel planes a 32-lane group reads fall on disjoint banks.
 // Result layout: lane (g, j) holds output channels 16c + 4g .. + 3 of pixel j.
 typedef float f32x2v __attribute__((ext_vector_type(2)));
-template <int CT16, bool UPCAT, int RW = 0, bool POOL = false>
+template <int CT16, bool UPCAT, int RW = 0, bool POOL = false, bool EX = false>
 __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Args A) {
   constexpr bool ROWSG = RW != 0;
   extern __shared__ __attribute__((aligned(16))) float tile[];      // 2 x 8 x tstride
@@ -698,8 +722,11 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
       for (int u = 0; u < 2; ++u) {
         const int oy = y0 + opy[u];
         float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
-        if (A.relu) v = fmaxf(v, 0.f);
-        if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + opx[u]];
+        if constexpr (EX) v = conv3_ex_tail(A, n, co, oy, opx[u], v);
+        else {
+          if (A.relu) v = fmaxf(v, 0.f);
+          if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + opx[u]];
+        }
         A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + opx[u] + A.out_off] = v;
       }
     }
@@ -1099,8 +1126,9 @@ static bool conv3x3_lds_ok(int Cout, int H, int W) {
   return (Cout + 31) / 32 <= 5 && W <= 64 && 256 % W == 0 && H % (256 / W) == 0 && 8 * (256 / W + 2) * (W + 2) <= 7 * 512;
 }
 
-template <bool UPCAT>
+template <bool UPCAT, bool EX = false>
 static hipError_t launch_conv3x3_lds(const Conv3Args& a, hipStream_t s) {
+  static_assert(!(UPCAT && EX), "poem_conv3x3_ex reads a bordered input");
   const int TR = 256 / a.W, cot = (a.Cout + 31) / 32;
   const dim3 grid((unsigned)(a.views * (a.H / TR))), block(512);
   if (conv3x3_m16(a.Cout)) {
@@ -1121,7 +1149,7 @@ static hipError_t launch_conv3x3_lds(const Conv3Args& a, hipStream_t s) {
         return hipGetLastError();
       }
     }
-#define POEM_CONVL16(CTV) hipLaunchKernelGGL((conv3x3_lds16_kernel<CTV, UPCAT>), grid, block, lds16, s, a)
+#define POEM_CONVL16(CTV) hipLaunchKernelGGL((conv3x3_lds16_kernel<CTV, UPCAT, 0, false, EX>), grid, block, lds16, s, a)
     switch ((a.Cout + 15) / 16) {
       case 1: POEM_CONVL16(1); break;
       case 3: POEM_CONVL16(3); break;
@@ -1131,7 +1159,7 @@ static hipError_t launch_conv3x3_lds(const Conv3Args& a, hipStream_t s) {
     return hipGetLastError();
   }
   const size_t lds = (size_t)2 * 8 * (TR + 2) * (a.W + 2) * sizeof(float);
-#define POEM_CONVL(CTV) hipLaunchKernelGGL((conv3x3_lds_kernel<CTV, UPCAT>), grid, block, lds, s, a)
+#define POEM_CONVL(CTV) hipLaunchKernelGGL((conv3x3_lds_kernel<CTV, UPCAT, false, EX>), grid, block, lds, s, a)
   switch (cot) {
     case 1: POEM_CONVL(1); break;
     case 2: POEM_CONVL(2); break;
@@ -1178,24 +1206,21 @@ extern "C" hipError_t poem_launch_upcat_conv3x3_pool_head(const float* a_half, i
 }
 
 // in (views, Cin, H+2, W+2) zero-bordered; out element strides as in Conv3Args.  stride 1 or 2, H, W even,
-// (H/stride)*(W/stride) % 32 == 0, Cin % 8 == 0.
-extern "C" hipError_t poem_launch_conv3x3(const float* in, const void* wp, const float* scale, const float* shift,
-                                          const float* res, float* out, int views, int Cin, int Cout, int H, int W,
-                                          int stride, int relu, long out_ns, int out_cs, int out_rs, int out_off,
-                                          hipStream_t s) {
+// (H/stride)*(W/stride) % 32 == 0, Cin % 8 == 0.  EX: the poem_conv3x3_ex epilogue (Conv3Args::res_pre ...), same routing.
+template <bool EX>
+static hipError_t launch_conv3x3_any(const Conv3Args& a, hipStream_t s) {
+  const int Cin = a.Cin, Cout = a.Cout, H = a.H, W = a.W, stride = a.stride, views = a.views;
   if (Cin % 8 || (stride != 1 && stride != 2) || H % stride || W % stride) return hipErrorInvalidValue;
   const int Ho = H / stride, Wo = W / stride;
   if ((Ho * Wo) % 32) return hipErrorInvalidValue;
   if ((size_t)Cin * (H + 2) * (W + 2) * 4 >= (1ull << 31)) return hipErrorInvalidValue;
-  Conv3Args a{in, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Cin)), scale, shift, res, out, Cin, Cout, H, W,
-              stride, relu, out_ns, out_cs, out_rs, out_off, views, nullptr, nullptr, 0, 0};
   const int cot = (Cout + 31) / 32, ptiles = Ho * Wo / 32;
-  if (stride == 1 && conv3x3_lds_ok(Cout, H, W)) return launch_conv3x3_lds<false>(a, s);
+  if (stride == 1 && conv3x3_lds_ok(Cout, H, W)) return launch_conv3x3_lds<false, EX>(a, s);
   const int pt = (ptiles % 2 == 0) ? 2 : 1;
   const int ct = (cot % 5 == 0) ? 5 : (cot % 3 == 0) ? 3 : (cot % 2 == 0) ? 2 : 1;
   const long items = (long)views * (cot / ct) * (ptiles / pt);
   const dim3 grid((unsigned)((items + 3) / 4)), block(256);
-#define POEM_CONV(CTV, PTV) hipLaunchKernelGGL((conv3x3_kernel<CTV, PTV>), grid, block, 0, s, a)
+#define POEM_CONV(CTV, PTV) hipLaunchKernelGGL((conv3x3_kernel<CTV, PTV, EX>), grid, block, 0, s, a)
   if (pt == 2) {
     if (ct == 5) POEM_CONV(5, 2); else if (ct == 3) POEM_CONV(3, 2); else if (ct == 2) POEM_CONV(2, 2); else POEM_CONV(1, 2);
   } else {
@@ -1203,6 +1228,29 @@ extern "C" hipError_t poem_launch_conv3x3(const float* in, const void* wp, const
   }
 #undef POEM_CONV
   return hipGetLastError();
+}
+
+extern "C" hipError_t poem_launch_conv3x3(const float* in, const void* wp, const float* scale, const float* shift,
+                                          const float* res, float* out, int views, int Cin, int Cout, int H, int W,
+                                          int stride, int relu, long out_ns, int out_cs, int out_rs, int out_off,
+                                          hipStream_t s) {
+  if (Cin % 8) return hipErrorInvalidValue;
+  Conv3Args a{in, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Cin)), scale, shift, res, out, Cin, Cout, H, W,
+              stride, relu, out_ns, out_cs, out_rs, out_off, views, nullptr, nullptr, 0, 0};
+  return launch_conv3x3_any<false>(a, s);
+}
+
+// poem_launch_conv3x3 with the residual by its own (view, channel, row, offset) strides, before (res_pre) or after the activation
+extern "C" hipError_t poem_launch_conv3x3_ex(const float* in, const void* wp, const float* scale, const float* shift,
+                                             const float* res, long res_ns, int res_cs, int res_rs, int res_off, int res_pre,
+                                             float* out, int views, int Cin, int Cout, int H, int W, int stride, int relu,
+                                             long out_ns, int out_cs, int out_rs, int out_off, hipStream_t s) {
+  if (Cin % 8) return hipErrorInvalidValue;
+  Conv3Args a{in, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Cin)), scale, shift, res, out, Cin, Cout, H, W,
+              stride, relu, out_ns, out_cs, out_rs, out_off, views, nullptr, nullptr, 0, 0};
+  a.res_pre = res_pre != 0;
+  a.res_ns = res_ns; a.res_cs = res_cs; a.res_rs = res_rs; a.res_off = res_off;
+  return launch_conv3x3_any<true>(a, s);
 }
 
 // out (views, Ca + Cb, H + 2 pad, W + 2 pad): channels [0, Ca) = bilinear x2 (align_corners=False) of a (views, Ca, H/2, W/2),

@@ -142,6 +142,19 @@ hipError_t poem_launch_pack_conv3x3(const float* w, int Cout, int Cin, void* out
 hipError_t poem_launch_conv3x3(const float* in, const void* wp, const float* scale, const float* shift, const float* res,
                                float* out, int views, int Cin, int Cout, int H, int W, int stride, int relu, long out_ns,
                                int out_cs, int out_rs, int out_off, hipStream_t s);
+hipError_t poem_launch_conv3x3_ex(const float* in, const void* wp, const float* scale, const float* shift, const float* res,
+                                  long res_ns, int res_cs, int res_rs, int res_off, int res_pre, float* out, int views, int Cin,
+                                  int Cout, int H, int W, int stride, int relu, long out_ns, int out_cs, int out_rs, int out_off,
+                                  hipStream_t s);
+size_t poem_conv1x1_packed_floats(int Cout, int Cin);
+hipError_t poem_launch_pack_conv1x1(const float* w, int Cout, int Cin, void* out, hipStream_t s);
+hipError_t poem_launch_conv1x1_nchw(const float* in, long in_ns, int in_cs, int in_rs, int in_off, const void* wp,
+                                    const float* shift, const float* res, long res_ns, int res_cs, int res_rs, int res_off,
+                                    float* out, long out_ns, int out_cs, int out_rs, int out_off, int views, int Cin, int Cout,
+                                    int H, int W, int relu, hipStream_t s);
+hipError_t poem_launch_hrnet_fuse(const float* const* ptrs, const long* ns, const int* cs, const int* rs, const int* off,
+                                  const int* shift, int nterms, float* out, long out_ns, int out_cs, int out_rs, int out_off,
+                                  int views, int C, int H, int W, hipStream_t s);
 hipError_t poem_launch_conv3x3_down2(const float* in, const void* wp, const float* scale, const float* shift, const float* res,
                                      float* out, int views, int Cin, int Cout, int H, int W, int relu, long out_ns, int out_cs,
                                      int out_rs, int out_off, hipStream_t s);

@@ -289,6 +289,74 @@ int poem_conv3x3(const float* in_padded, const void* w_packed, const float* scal
   return POEM_OK;
 }
 
+// (n, c, y, x) -> p[n * vs + c * cs + y * rs + x + off] stays inside the view's c * cs floats for every channel: a plain map or
+// the interior of a bordered one (the kernels read the input through a per-view buffer descriptor of that size)
+static bool map_ok(int64_t vs, int cs, int rs, int off, int h, int w) {
+  return vs >= 0 && cs > 0 && rs >= w && off >= 0 && (int64_t)(h - 1) * rs + (w - 1) + off < (int64_t)cs;
+}
+
+int poem_conv3x3_ex(const float* in_padded, const void* w_packed, const float* scale, const float* shift, const float* residual,
+                    int64_t res_view_stride, int res_ch_stride, int res_row_stride, int res_offset, int res_before_act, float* out,
+                    int views, int cin, int cout, int h, int w, int stride, int relu, int64_t out_view_stride, int out_ch_stride,
+                    int out_row_stride, int out_offset, void* stream) {
+  if (!in_padded || !w_packed || !scale || !shift || !out || views <= 0 || cin <= 0 || cin % 8 || cout <= 0) return POEM_E_ARG;
+  if ((stride != 1 && stride != 2) || h <= 0 || w <= 0 || h % stride || w % stride || ((h / stride) * (w / stride)) % 32)
+    return POEM_E_UNSUPPORTED;
+  if ((uint64_t)cin * (uint64_t)(h + 2) * (uint64_t)(w + 2) * 4 >= (1ull << 31)) return POEM_E_UNSUPPORTED;
+  if (residual && !map_ok(res_view_stride, res_ch_stride, res_row_stride, res_offset, h / stride, w / stride)) return POEM_E_ARG;
+  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / stride, w / stride)) return POEM_E_ARG;
+  HIPCHK(poem_launch_conv3x3_ex(in_padded, w_packed, scale, shift, residual, (long)res_view_stride, res_ch_stride, res_row_stride,
+                                res_offset, res_before_act, out, views, cin, cout, h, w, stride, relu, (long)out_view_stride,
+                                out_ch_stride, out_row_stride, out_offset, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+size_t poem_conv1x1_packed_bytes(int cout, int cin) {
+  if (cout <= 0 || cin <= 0 || cin % 8) return 0;
+  return poem_conv1x1_packed_floats(cout, cin) * sizeof(float);
+}
+
+int poem_pack_conv1x1(const float* w_oi, int cout, int cin, void* packed, void* stream) {
+  if (!w_oi || !packed || cout <= 0 || cin <= 0 || cin % 8) return POEM_E_ARG;
+  HIPCHK(poem_launch_pack_conv1x1(w_oi, cout, cin, packed, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_conv1x1(const float* in, int64_t in_view_stride, int in_ch_stride, int in_row_stride, int in_offset, const void* w_packed,
+                 const float* shift, const float* residual, int64_t res_view_stride, int res_ch_stride, int res_row_stride,
+                 int res_offset, float* out, int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset,
+                 int views, int cin, int cout, int h, int w, int relu, void* stream) {
+  if (!in || !w_packed || !out || views <= 0 || cin <= 0 || cin % 8 || cout <= 0) return POEM_E_ARG;
+  if (h <= 0 || w <= 0 || ((int64_t)h * w) % 32 || (int64_t)h * w >= (1ll << 29)) return POEM_E_UNSUPPORTED;
+  if (!map_ok(in_view_stride, in_ch_stride, in_row_stride, in_offset, h, w)) return POEM_E_ARG;
+  if ((uint64_t)cin * (uint64_t)in_ch_stride * 4 >= (1ull << 31)) return POEM_E_UNSUPPORTED;
+  if (residual && !map_ok(res_view_stride, res_ch_stride, res_row_stride, res_offset, h, w)) return POEM_E_ARG;
+  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h, w)) return POEM_E_ARG;
+  HIPCHK(poem_launch_conv1x1_nchw(in, (long)in_view_stride, in_ch_stride, in_row_stride, in_offset, w_packed, shift, residual,
+                                  (long)res_view_stride, res_ch_stride, res_row_stride, res_offset, out, (long)out_view_stride,
+                                  out_ch_stride, out_row_stride, out_offset, views, cin, cout, h, w, relu, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_hrnet_fuse(const poem_fuse_term_t* terms, int nterms, float* out, int64_t out_view_stride, int out_ch_stride,
+                    int out_row_stride, int out_offset, int views, int channels, int h, int w, void* stream) {
+  if (!terms || !out || nterms < 2 || nterms > 4 || views <= 0 || channels <= 0 || h <= 0 || w <= 0) return POEM_E_ARG;
+  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h, w)) return POEM_E_ARG;
+  const float* ptrs[4];
+  long ns[4];
+  int cs[4], rs[4], off[4], shift[4];
+  for (int k = 0; k < nterms; ++k) {
+    const poem_fuse_term_t& t = terms[k];
+    if (!t.data || t.shift < 0 || t.shift > 3) return POEM_E_ARG;
+    if (!map_ok(t.view_stride, t.ch_stride, t.row_stride, t.offset, ((h - 1) >> t.shift) + 1, ((w - 1) >> t.shift) + 1)) return POEM_E_ARG;
+    ptrs[k] = t.data; ns[k] = (long)t.view_stride; cs[k] = t.ch_stride; rs[k] = t.row_stride; off[k] = t.offset; shift[k] = t.shift;
+  }
+  if ((int64_t)views * channels * h * w > (int64_t)0x7fffffff * 256) return POEM_E_UNSUPPORTED;
+  HIPCHK(poem_launch_hrnet_fuse(ptrs, ns, cs, rs, off, shift, nterms, out, (long)out_view_stride, out_ch_stride, out_row_stride,
+                                out_offset, views, channels, h, w, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 int poem_conv3x3_down2(const float* in, const void* w_packed, const float* scale, const float* shift, const float* residual,
                        float* out, int views, int cin, int cout, int h, int w, int relu, int64_t out_view_stride,
                        int out_ch_stride, int out_row_stride, int out_offset, void* stream) {

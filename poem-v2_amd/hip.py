@@ -37,6 +37,12 @@ class PoemLossCfg(ctypes.Structure):
                 ("parametric", ctypes.c_int32), ("center_idx", ctypes.c_int32), ("img_h", ctypes.c_int32), ("img_w", ctypes.c_int32)]
 
 
+class PoemFuseTerm(ctypes.Structure):
+    """include/poem_hip.h poem_fuse_term_t"""
+    _fields_ = [("data", ctypes.c_void_p), ("view_stride", ctypes.c_int64), ("ch_stride", ctypes.c_int32),
+                ("row_stride", ctypes.c_int32), ("offset", ctypes.c_int32), ("shift", ctypes.c_int32)]
+
+
 LOSS_NTERMS = 10             # include/poem_hip.h POEM_LOSS_NTERMS
 
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
@@ -98,6 +104,11 @@ SIGNATURES = {
     "poem_conv3x3_packed_bytes": (_sz, [_i, _i]),
     "poem_pack_conv3x3": (_i, [_vp, _i, _i, _vp, _vp]),
     "poem_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp]),
+    "poem_conv3x3_ex": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp]),
+    "poem_conv1x1_packed_bytes": (_sz, [_i, _i]),
+    "poem_pack_conv1x1": (_i, [_vp, _i, _i, _vp, _vp]),
+    "poem_conv1x1": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "poem_hrnet_fuse": (_i, [_vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "poem_set_decode_option": (_i, [ctypes.c_char_p, _i]),
     "poem_conv3x3_down2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp]),
     "poem_upsample2_concat_pad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),

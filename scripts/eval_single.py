@@ -252,12 +252,13 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
 
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
                     n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
-                    mano_assets=None):
+                    mano_assets=None, backbone_engine="torch"):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
     (``PtEmbedMultiviewStereoV2``: HRNet on PyTorch-ROCm -> decode / heat maps / DLT / head on HIP) and the device metrics
     against the records' ``master_joints_3d`` / ``master_verts_3d`` (lib/models/POEM.py:596-610 upstream).
+    ``backbone_engine``: ``"hip"`` runs HRNet on the project's own convolution kernels (model key BACKBONE.ENGINE).
     ``losses``: MANO's (16,778) joint regressor (``--losses --j-regressor``): every batch's loss terms (upstream's ``compute_loss``,
     value only) feed the model's ``loss_metric`` on the device and the result gains their batch-size-weighted averages.
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
@@ -283,6 +284,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         model_node["LOSS"] = loss_node(cfg)
     if mano_assets:
         model_node["MANO_ASSETS"] = mano_assets
+    if backbone_engine != "torch":
+        model_node["BACKBONE"] = {"ENGINE": backbone_engine}
     model = pk.build_model(pk.CN(model_node))
     if losses is not None:
         model.set_j_regressor(losses)
@@ -393,7 +396,8 @@ def main(args):
         res = evaluate_shards(cfg, view_range, args.model, device, args.shards, args.dataset, reload=args.reload,
                               epoch_size=args.epoch_size, batch_size=args.batch_size, template=args.template,
                               dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw,
-                              losses=j_regressor, mano_assets=mano_assets)
+                              losses=j_regressor, mano_assets=mano_assets,
+                              backbone_engine=getattr(args, "backbone_engine", "torch"))
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
@@ -455,6 +459,10 @@ def build_cli():
                         help="MANO's five arrays (v_template, shapedirs, posedirs, J_regressor, weights; on a licensed machine: the fields "
                              "of MANO_RIGHT.pkl).  The head takes its zero-pose template and, for medium_MANO, its MANO layer from them: "
                              "--reload needs no --template, and medium_MANO runs (head config key MANO_ASSETS).")
+    # (absent from the namespace unless given: the host tests pin the namespace of a plain command line key by key)
+    parser.add_argument("--backbone-engine", choices=("torch", "hip"), default=argparse.SUPPRESS,
+                        help="with --shards: what runs HRNet-W40 -- torch (PyTorch-ROCm / MIOpen, the default) or hip (the project's own "
+                             "gfx950 convolution kernels; model key BACKBONE.ENGINE).  The other scopes start behind the backbone.")
     return parser
 
 

@@ -1,6 +1,13 @@
 #!/usr/bin/env python
-"""A/B of the PyTorch-ROCm HRNet (E2E scope plumbing): memory format and MIOpen find mode.  Not part of the hot path."""
+"""HRNet-W40 forward time on one GPU: ``--engine torch`` (PyTorch-ROCm / MIOpen) or ``--engine hip`` (the project's own
+convolution kernels, poem_v2_amd/backbone.py).  Prints one JSON line: per-forward median / min / max over ``--steps`` timed
+forwards (device events around each), images/s, and the fraction of the fp32 matrix peak from the FLOP count of
+``backbone._conv_specs`` at this input size.  ``--miopen-ab``: the older A/B of the torch engine's memory format and MIOpen
+find mode."""
+import argparse
+import json
 import os
+import statistics
 import sys
 import time
 
@@ -9,30 +16,82 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import poem_v2_amd as pk  # noqa: E402,F401
-from poem_v2_amd.backbone import HRNet, seeded_hrnet_state_dict  # noqa: E402
+from poem_v2_amd.backbone import HipPlan, HRNet, seeded_hrnet_state_dict  # noqa: E402
 
-dev = torch.device("cuda:0")
-views = int(sys.argv[1]) if len(sys.argv) > 1 else 256
-img = pk.inputs.synthetic_images(views, seed=1).to(dev)
-for fmt in ("contiguous", "channels_last"):
-    for bench in (False, True):
-        torch.backends.cudnn.benchmark = bench
-        net = HRNet(state_dict=seeded_hrnet_state_dict(0), device=dev)
-        x = img
-        if fmt == "channels_last":
-            x = img.contiguous(memory_format=torch.channels_last)
-            for c in net._convs.values():
-                c.weight = c.weight.contiguous(memory_format=torch.channels_last)
-        t0 = time.perf_counter()
-        net(x)
-        torch.cuda.synchronize()
-        first = time.perf_counter() - t0
-        net(x)
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        for _ in range(3):
-            ys = net(x)
-        torch.cuda.synchronize()
-        dt = (time.perf_counter() - t0) / 3
-        print(f"{fmt:14s} miopen-benchmark={bench!s:5s} first call {first:6.1f} s, steady {dt * 1e3:7.1f} ms / {views} images "
-              f"({views / dt:7.0f} img/s)  out0 {tuple(ys[0].shape)} {ys[0].is_contiguous()}", flush=True)
+FP32_MATRIX_PEAK = 157.3e12
+
+
+def hrnet_flops(H, W):
+    """multiply-adds x 2 of every convolution, per view (the padded stem channels are not counted)"""
+    total = 0
+    for op in HipPlan(1, H, W).ops:
+        if "conv" in op:
+            k = 1 if op["kind"] == "conv1" else 3
+            cin = 3 if op["conv"] == "conv1" else op["in"].c
+            total += 2 * k * k * cin * op["out"].c * op["out"].h * op["out"].w
+    return total
+
+
+def miopen_ab(views, dev):
+    img = pk.inputs.synthetic_images(views, seed=1).to(dev)
+    for fmt in ("contiguous", "channels_last"):
+        for bench in (False, True):
+            torch.backends.cudnn.benchmark = bench
+            net = HRNet(state_dict=seeded_hrnet_state_dict(0), device=dev)
+            x = img
+            if fmt == "channels_last":
+                x = img.contiguous(memory_format=torch.channels_last)
+                for c in net._convs.values():
+                    c.weight = c.weight.contiguous(memory_format=torch.channels_last)
+            t0 = time.perf_counter()
+            net(x)
+            torch.cuda.synchronize()
+            first = time.perf_counter() - t0
+            net(x)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(3):
+                ys = net(x)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / 3
+            print(f"{fmt:14s} miopen-benchmark={bench!s:5s} first call {first:6.1f} s, steady {dt * 1e3:7.1f} ms / {views} images "
+                  f"({views / dt:7.0f} img/s)  out0 {tuple(ys[0].shape)} {ys[0].is_contiguous()}", flush=True)
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__)
+    ap.add_argument("views", type=int, nargs="?", default=256)
+    ap.add_argument("--engine", choices=("torch", "hip"), default="torch")
+    ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"))
+    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--miopen-ab", action="store_true")
+    a = ap.parse_args()
+    dev = torch.device("cuda:0")
+    if a.miopen_ab:
+        return miopen_ab(a.views, dev)
+    H, W = a.size
+    img = (0.5 * torch.randn(a.views, 3, H, W, generator=torch.Generator().manual_seed(1))).to(dev)
+    net = HRNet({"ENGINE": a.engine}, state_dict=seeded_hrnet_state_dict(0), device=dev)
+    for _ in range(a.warmup):
+        ys = net(img)
+    torch.cuda.synchronize()
+    times = []
+    for _ in range(a.steps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        ys = net(img)
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    med = statistics.median(times)
+    flops = hrnet_flops(H, W) * a.views
+    print(json.dumps({"engine": a.engine, "views": a.views, "size": [H, W], "steps": a.steps, "ms_median": round(med, 3),
+                      "ms_min": round(min(times), 3), "ms_max": round(max(times), 3), "images_per_s": round(a.views / med * 1e3, 1),
+                      "gflop_per_view": round(flops / a.views / 1e9, 2), "tflops": round(flops / med / 1e9, 2),
+                      "fp32_matrix_peak_fraction": round(flops / (med * 1e-3) / FP32_MATRIX_PEAK, 4),
+                      "checksum": float(sum(y.double().abs().mean() for y in ys))}))
+
+
+if __name__ == "__main__":
+    main()
