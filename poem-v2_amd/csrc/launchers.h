@@ -47,6 +47,9 @@ hipError_t poem_launch_project_uv(const float* bps, const float* centre, const i
                                   const float* extr, float* inv_scratch, float* uv, int views, int fh, int fw, int S, int img_w,
                                   int img_h, hipStream_t s);
 hipError_t poem_launch_grid_sample(const float* x, const float* uv, float* g, int views, int C, int fh, int fw, int S, hipStream_t s);
+// staged: 1 = planes staged in LDS (at most 2048 pixels), 0 = taps read from global memory, < 0 = the launcher's own choice
+hipError_t poem_launch_grid_sample_ex(const float* x, const float* uv, float* g, int views, int C, int fh, int fw, int S, int staged,
+                                      hipStream_t s);
 hipError_t poem_launch_merge_reduce(const float* h2, const int* offs, float* m, int B, int S, int HALF, hipStream_t s);
 hipError_t poem_launch_merge_finalize(const float* g, const float* y, const int* offs, float* out, int B, int S, int C,
                                       hipStream_t s);

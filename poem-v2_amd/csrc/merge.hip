@@ -22,9 +22,15 @@
 // merge_tail_kernel: a block owns 64 basis points of one sample: dot / weighted sum over the views (merge_features_mv;
 // N = 1: the master row itself), merge_net[1] as two LDS-resident GEMMs, / N, + q1 -> bps_feat.
 //
-// Arithmetic: every sampled value, every Linear output element and every reduction is the same fma chain as in the
-// unfused kernels (sample.hip, gemm.hip) except the order of the dot-product reduction over channels (16-lane groups
-// here, a full-wave tree there); the two paths agree to fp32 round-off (tests/test_hip_parity.py).
+// Arithmetic: every Linear output element and every reduction is the same fma chain as in the unfused kernels (gemm.hip,
+// sample.hip) except the order of the dot-product reduction over channels (16-lane groups here, a full-wave tree there).  A
+// sampled value is the same four-term sum nw, ne, sw, se of the same taps and weights, but NOT the same chain: here it is written
+// with fmaf (the nw product rounded, three fused steps); grid_sample_kernel leaves the contraction to the compiler, which rounds
+// the ne product and fuses the nw one onto it -- about 15 % of the values differ, by one ulp, rarely two (both within
+// 4 * 2^-24 * sum |w| |tap| of the exact sum).  The two paths agree to fp32 round-off (tests/test_hip_parity.py,
+// tests/test_sampling_forms.py).
+//   The unfused path takes any map: up to 2048 pixels grid_sample_kernel stages its 8 planes in LDS, above that (this front end
+// serves up to 65536 pixels, the range of the 16-bit tap pixels) it reads the four taps from global memory -- same expression.
 #include "common.h"
 #include <algorithm>
 

@@ -322,16 +322,21 @@ __global__ void project_kernel(const float* __restrict__ bps, const float* __res
 // Bilinear sampling, zero padding.  Block = (view, group of CG channels): the CG planes (fh*fw floats each) are
 // staged in LDS once, every thread then walks the point axis (consecutive threads -> consecutive s: coalesced
 // reads of uv and coalesced writes of g[v, c, s]).
-template <int CG>
+//   STAGED = false: the four taps are read from global memory instead -- the form for maps whose CG planes do not fit in the
+// 64 KB of LDS a kernel gets without an opt-in (CG = 8: more than 2048 pixels; the fused front end of merge.hip takes maps of
+// up to 65536).  Same expression in the same order: the two forms give the same bits.
+template <int CG, bool STAGED>
 __global__ __launch_bounds__(256) void grid_sample_kernel(const float* __restrict__ x, const float* __restrict__ uv,
                                                           float* __restrict__ g, int C, int fh, int fw, int S) {
-  extern __shared__ float planes[];  // CG * fh * fw
+  extern __shared__ float planes[];  // CG * fh * fw (STAGED)
   const int hw = fh * fw;
   const int v = blockIdx.y;
   const int c0 = blockIdx.x * CG;
   const float* xv = x + ((size_t)v * C + c0) * hw;
-  for (int i = threadIdx.x; i < CG * hw; i += blockDim.x) planes[i] = (c0 + i / hw < C) ? xv[i] : 0.f;
-  __syncthreads();
+  if constexpr (STAGED) {
+    for (int i = threadIdx.x; i < CG * hw; i += blockDim.x) planes[i] = (c0 + i / hw < C) ? xv[i] : 0.f;
+    __syncthreads();
+  }
   const float2* uvv = reinterpret_cast<const float2*>(uv) + (size_t)v * S;
   for (int s = threadIdx.x; s < S; s += blockDim.x) {
     const float2 p = uvv[s];
@@ -348,7 +353,7 @@ __global__ __launch_bounds__(256) void grid_sample_kernel(const float* __restric
 #pragma unroll
     for (int c = 0; c < CG; ++c) {
       if (c0 + c >= C) break;
-      const float* pl = planes + c * hw;
+      const float* pl = (STAGED ? planes : xv) + (size_t)c * hw;
       // same accumulation order as ATen's grid_sampler_2d: nw, ne, sw, se
       float acc = pl[i_nw] * w_nw;
       acc += pl[i_ne] * w_ne;
@@ -357,6 +362,19 @@ __global__ __launch_bounds__(256) void grid_sample_kernel(const float* __restric
       g[((size_t)v * C + c0 + c) * S + s] = acc;
     }
   }
+}
+
+// staged: 1 = planes in LDS, 0 = taps from global memory, < 0 = LDS where the CG planes fit in 64 KB (no opt-in needed)
+static constexpr int GS_CG = 8;
+static hipError_t launch_grid_sample(const float* x, const float* uv, float* g, int views, int C, int fh, int fw, int S, int staged,
+                                     hipStream_t s) {
+  const size_t lds = (size_t)GS_CG * fh * fw * sizeof(float);
+  if (staged < 0) staged = lds <= 64 * 1024;
+  if (staged && lds > 64 * 1024) return hipErrorInvalidValue;
+  const dim3 grid((C + GS_CG - 1) / GS_CG, views);
+  if (staged) hipLaunchKernelGGL((grid_sample_kernel<GS_CG, true>), grid, dim3(256), lds, s, x, uv, g, C, fh, fw, S);
+  else hipLaunchKernelGGL((grid_sample_kernel<GS_CG, false>), grid, dim3(256), 0, s, x, uv, g, C, fh, fw, S);
+  return hipGetLastError();
 }
 
 extern "C" hipError_t poem_launch_invert_extr(const float* extr, float* inv, int views, hipStream_t s) {
@@ -376,10 +394,13 @@ extern "C" hipError_t poem_launch_project_uv(const float* bps, const float* cent
 }
 extern "C" hipError_t poem_launch_grid_sample(const float* x, const float* uv, float* g, int views, int C, int fh, int fw, int S,
                                               hipStream_t s) {
-  constexpr int CG = 8;
-  hipLaunchKernelGGL((grid_sample_kernel<CG>), dim3((C + CG - 1) / CG, views), dim3(256), CG * fh * fw * sizeof(float),
-                     s, x, uv, g, C, fh, fw, S);
-  return hipGetLastError();
+  return launch_grid_sample(x, uv, g, views, C, fh, fw, S, -1, s);
+}
+
+// ... with the form chosen by the caller (tests: the two forms against each other at a size where both can run)
+extern "C" hipError_t poem_launch_grid_sample_ex(const float* x, const float* uv, float* g, int views, int C, int fh, int fw, int S,
+                                                 int staged, hipStream_t s) {
+  return launch_grid_sample(x, uv, g, views, C, fh, fw, S, staged, s);
 }
 
 extern "C" hipError_t poem_launch_project_sample(const float* x, const float* bps, const float* centre,
@@ -390,10 +411,7 @@ extern "C" hipError_t poem_launch_project_sample(const float* x, const float* bp
   // NB upstream names the pair (w, h) = inp_img_shape; the x coordinate is divided by the first entry.
   hipLaunchKernelGGL(project_kernel, dim3((S + 255) / 256, views), dim3(256), 0, s, bps, centre, view_sample, intr,
                      inv_scratch, uv, views, S, fw, fh, 1.0f / (float)img_w, 1.0f / (float)img_h);
-  constexpr int CG = 8;
-  hipLaunchKernelGGL((grid_sample_kernel<CG>), dim3((C + CG - 1) / CG, views), dim3(256), CG * fh * fw * sizeof(float),
-                     s, x, uv, g, C, fh, fw, S);
-  return hipGetLastError();
+  return launch_grid_sample(x, uv, g, views, C, fh, fw, S, -1, s);
 }
 
 // ---------------------------------------------------------------------------------------------------------

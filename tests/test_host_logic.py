@@ -420,6 +420,29 @@ def test_chain_args_ctypes_mirror_matches_chain_h():
     assert [(n, t) for n, t in ChainArgs._fields_] == fields
 
 
+def test_sampling_args_ctypes_mirrors_match_merge_h():
+    """tests/util.py's SampleMergeArgs, SampleGroupArgs and MergeTailArgs are what test_sampling_forms.py hands the fused sampling
+    launchers by pointer: hold them against csrc/merge.h field by field (order, name, pointer / int / nested struct)."""
+    import ctypes
+    import util
+    src = open(os.path.join(ROOT, "poem-v2_amd", "csrc", "merge.h")).read()
+    for name, count in (("SampleMergeArgs", 19), ("SampleGroupArgs", 6), ("MergeTailArgs", 14)):
+        body = re.search(r"struct %s\s*\{(.*?)\};" % name, src, re.S).group(1)
+        body = re.sub(r"//[^\n]*", "", body)
+        fields = []
+        for decl in (d.strip() for d in body.split(";")):
+            if not decl:
+                continue
+            m = re.match(r"^((?:const\s+)?[A-Za-z_]\w*)\s*(\*?)\s*([A-Za-z_]\w*)$", decl.split(",")[0].strip())
+            assert m, decl
+            base, star = m.group(1).replace("const", "").strip(), m.group(2)
+            kind = ctypes.c_void_p if star else {"int": ctypes.c_int, "SampleMergeArgs": util.SampleMergeArgs}[base]
+            for n in [m.group(3)] + [n.strip() for n in decl.split(",")[1:]]:
+                fields.append((n, kind))
+        assert len(fields) == count, (name, fields)
+        assert [(n, t) for n, t in getattr(util, name)._fields_] == fields, name
+
+
 def test_bench_refuses_to_report_n_gpus_from_fewer_devices():
     """``python bench.py --gpus N`` without a launcher starts its own ranks; with fewer than N devices it must fail loudly,
     never print a line that claims N GPUs (here: no GPU at all)."""

@@ -216,3 +216,21 @@ class ChainArgs(ctypes.Structure):
                 ("wf4", _P), ("bf4", _P), ("wreg2", _P), ("breg2", _P), ("xyz_in", _P), ("xyz_out", _P), ("wout", _P), ("bout", _P),
                 ("ln2_g", _P), ("ln2_b", _P), ("y3", _P), ("ldy3", _I),
                 ("native_delta", ctypes.c_longlong)]
+
+
+# ---- ctypes mirrors of the fused sampling stage's argument blocks (poem-v2_amd/csrc/merge.h), field for field: what
+# tests/test_sampling_forms.py hands poem_launch_sample_merge / _sample_group / _merge_tail by pointer.
+class SampleMergeArgs(ctypes.Structure):
+    _fields_ = [("xt", _P), ("tab", _P), ("tabo", _P), ("view_sample", _P), ("offs", _P),
+                ("w0", _P), ("b0", _P), ("w1", _P), ("b1", _P), ("h2", _P), ("q1", _P),
+                ("views", _I), ("S", _I), ("hw", _I), ("B", _I), ("h2_tiled", _I),
+                ("views_dev", _P), ("group_min_views", _I), ("xcd_order", _I)]
+
+
+class SampleGroupArgs(ctypes.Structure):
+    _fields_ = [("sm", SampleMergeArgs), ("w2", _P), ("b2", _P), ("w3", _P), ("b3", _P), ("out", _P)]
+
+
+class MergeTailArgs(ctypes.Structure):
+    _fields_ = [("h2", _P), ("q1", _P), ("offs", _P), ("w0", _P), ("b0", _P), ("w1", _P), ("b1", _P), ("out", _P),
+                ("B", _I), ("S", _I), ("h2_tiled", _I), ("group_min_views", _I), ("views_dev", _P), ("views", _I)]
