@@ -440,6 +440,41 @@ int poem_hrnet_fuse(const poem_fuse_term_t* terms, int nterms, float* out, int64
                     int out_row_stride, int out_offset, int views, int channels, int h, int w, void* stream);
 int poem_upsample2_concat_pad(const float* a, int ca, const float* b, int cb, float* out, int views, int h, int w, int pad,
                               void* stream);
+/* The ResNet-18/34/50 backbones (lib/models/backbones/resnet.py upstream) and the non-HRNet decode
+ * branch (lib/models/POEM.py:168-181,205-206) need four operators besides the ones above -- BasicBlock and Bottleneck bodies run
+ * on poem_conv3x3_ex and poem_conv1x1 as they are.  Same contract: exact fp32 on v_mfma_f32_32x32x2_f32 in a fixed k order (bit-
+ * reproducible; a view's result does not depend on the other views of the launch), maps as above, stream-ordered, no
+ * allocation, refusals before any store.  POEM_E_ARG: null pointers, cin % 8, a map outside its plane; POEM_E_UNSUPPORTED: odd
+ * h or w, (h/2)*(w/2) % 32 (the pooling operator: odd h or w only), cout % 32 (stem), a view of 2 GiB or more.  h, w are the INPUT's.
+ * poem_pack_conv7x7 / poem_conv7x7_s2: the stem (resnet.py:161-163,209-211).  Weights (cout,3,7,7) OIHW packed once
+ *   (poem_conv7x7_packed_bytes bytes): an implicit GEMM with K = 3*49 = 147 zero-padded to 152.  in (views,3,h,w) plain; out map
+ *   (views,cout,h/2,w/2) = relu(conv7x7(in, padding 3, stride 2)*scale[c] + shift[c]), ReLU as torch's (NaN propagates).  A
+ *   padding tap is a zero operand, never a read outside the image.
+ * poem_maxpool3x3_s2: nn.MaxPool2d(3, 2, 1), map (views,channels,h,w) -> map (views,channels,h/2,w/2); the padding counts as
+ *   -inf; torch's bits: the window is scanned in (ky,kx) order and a value replaces the maximum when val > max || isnan(val).
+ * poem_conv1x1_s2: the shortcut of the first block of layer2..4 (resnet.py:188-191): out(y,x) = W*in(2y,2x) + shift, no
+ *   activation; in map (views,cin,h,w), out map (views,cout,h/2,w/2); w_packed is the poem_pack_conv1x1 image; shift may be null.
+ * poem_maxpool2_conv1x1: x (views,cin,h,w) plain -> max_pool2d(2,2) (torch's rule, as above) -> 1x1 convolution (w_packed: the
+ *   poem_pack_conv1x1 image of (cout,cin); bias (cout)) -> act 0 none (feat_in, POEM.py:180-181) | 1 sigmoid (uv_out, :205-206) ->
+ *   out (views,cout,h/2,w/2) plain.  Any cout.
+ * poem_upsample2_concat_pad_staged: poem_upsample2_concat_pad with pad = 1 whose interpolation is rounded as poem_upcat_conv3x3
+ *   rounds it while it stages its input (the tap weights multiplied out, one multiply and three fmas; the older operator nests
+ *   the two directions as torch does): poem_conv3x3 of the result equals poem_upcat_conv3x3 bit for bit, so the fused and the
+ *   two-launch route of the non-HRNet decode branch return the same bits. */
+size_t poem_conv7x7_packed_bytes(int cout);
+int poem_pack_conv7x7(const float* w_oihw, int cout, void* packed, void* stream);
+int poem_conv7x7_s2(const float* in, const void* w_packed, const float* scale, const float* shift, float* out,
+                    int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset, int views, int cout, int h, int w,
+                    void* stream);
+int poem_maxpool3x3_s2(const float* in, int64_t in_view_stride, int in_ch_stride, int in_row_stride, int in_offset, float* out,
+                       int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset, int views, int channels, int h,
+                       int w, void* stream);
+int poem_conv1x1_s2(const float* in, int64_t in_view_stride, int in_ch_stride, int in_row_stride, int in_offset, const void* w_packed,
+                    const float* shift, float* out, int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset,
+                    int views, int cin, int cout, int h, int w, void* stream);
+int poem_maxpool2_conv1x1(const float* x, const void* w_packed, const float* bias, float* out, int views, int cin, int cout, int h,
+                          int w, int act, void* stream);
+int poem_upsample2_concat_pad_staged(const float* a, int ca, const float* b, int cb, float* out, int views, int h, int w, void* stream);
 /* A stride-2 ConvBlock of feat_decode (POEM.py:183-189: padding 1, stride 2) straight from the UNBORDERED input
  * (views,cin,h,w): LDS-staged, 16-channel matrix tiles; out / residual addressing as poem_conv3x3.  POEM_E_UNSUPPORTED for
  * shapes other than HRNet-W40's three (cout, h = w) = (80, 64), (160, 32), (320, 16): use poem_conv3x3(stride 2) on a

@@ -347,30 +347,33 @@ class _HipEngine:
     def __init__(self, convs, device):
         from . import hip
         from .decode import _pad32
-        self.hip, self.device = hip, torch.device(device)
-        L = hip.lib()
+        self.hip, self.device, self._pad32 = hip, torch.device(device), _pad32
         self.w = {}                                      # conv key -> (packed weights, scale | None, shift, cin, cout)
         for name, c in convs.items():
-            w = c.weight.to(self.device)
-            if name == "conv1":
-                w = stem_weight(w)
-            cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
-            w = w.contiguous()
-            bias = c.bias.to(self.device)
-            if k == 3:
-                packed = torch.empty(L.poem_conv3x3_packed_bytes(cout, cin), dtype=torch.uint8, device=self.device)
-                hip.check(L.poem_pack_conv3x3(hip.ptr(w), cout, cin, packed.data_ptr(), hip.stream()), "poem_pack_conv3x3")
-                self.w[name] = (packed, _pad32(torch.ones_like(bias)), _pad32(bias), cin, cout)   # the scale is in the weight
-            else:
-                packed = torch.empty(L.poem_conv1x1_packed_bytes(cout, cin), dtype=torch.uint8, device=self.device)
-                hip.check(L.poem_pack_conv1x1(hip.ptr(w), cout, cin, packed.data_ptr(), hip.stream()), "poem_pack_conv1x1")
-                self.w[name] = (packed, None, bias.contiguous(), cin, cout)
+            self.w[name] = self._pack(name, c.weight.to(self.device), c.bias.to(self.device))
         self._plans = {}
+
+    def _pack(self, name, w, bias):
+        hip, L = self.hip, self.hip.lib()
+        if name == "conv1":
+            w = stem_weight(w)
+        cout, cin, k = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+        w = w.contiguous()
+        if k == 3:
+            packed = torch.empty(L.poem_conv3x3_packed_bytes(cout, cin), dtype=torch.uint8, device=self.device)
+            hip.check(L.poem_pack_conv3x3(hip.ptr(w), cout, cin, packed.data_ptr(), hip.stream()), "poem_pack_conv3x3")
+            return (packed, self._pad32(torch.ones_like(bias)), self._pad32(bias), cin, cout)   # the scale is in the weight
+        packed = torch.empty(L.poem_conv1x1_packed_bytes(cout, cin), dtype=torch.uint8, device=self.device)
+        hip.check(L.poem_pack_conv1x1(hip.ptr(w), cout, cin, packed.data_ptr(), hip.stream()), "poem_pack_conv1x1")
+        return (packed, None, bias.contiguous(), cin, cout)
+
+    def _make_plan(self, views, H, W):
+        return HipPlan(views, H, W)
 
     def plan(self, views, H, W):
         key = (views, H, W)
         if key not in self._plans:
-            plan = HipPlan(views, H, W)
+            plan = self._make_plan(views, H, W)
             bufs = [torch.zeros(plan.buffer_shape(b), dtype=torch.float32, device=self.device) for b in range(len(plan.buffers))]
             self._plans[key] = (plan, bufs, self._bind(plan, bufs))
         return self._plans[key]
@@ -392,23 +395,27 @@ class _HipEngine:
                     t.data, t.view_stride, t.ch_stride, t.row_stride, t.offset, t.shift = ptr(m), ns, cs, rs, off, shift
                 calls.append(("poem_hrnet_fuse", L.poem_hrnet_fuse, out.buf, [terms, len(terms), ptr(out), *out.strides, views, out.c, out.h, out.w]))
                 continue
-            packed, scale, shift, cin, cout = self.w[op["conv"]]
-            x, res = op["in"], op["res"]
-            assert (cin, cout) == (x.c, out.c), op["conv"]
-            rptr, rstr = (ptr(res), res.strides) if res is not None else (None, (0, 0, 0, 0))
-            if kind == "conv3":
-                args = [ptr(x), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), rptr, *rstr, 1, ptr(out), views, cin, cout,
-                        x.h, x.w, op["stride"], int(op["relu"]), *out.strides]
-                calls.append(("poem_conv3x3_ex", L.poem_conv3x3_ex, out.buf, args))
-            elif kind == "down2":
-                args = [ptr(x), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), None, ptr(out), views, cin, cout, x.h, x.w,
-                        int(op["relu"]), *out.strides]
-                calls.append(("poem_conv3x3_down2", L.poem_conv3x3_down2, out.buf, args))
-            else:
-                args = [ptr(x), *x.strides, packed.data_ptr(), shift.data_ptr(), rptr, *rstr, ptr(out), *out.strides, views, cin, cout,
-                        x.h, x.w, int(op["relu"])]
-                calls.append(("poem_conv1x1", L.poem_conv1x1, out.buf, args))
+            calls.append(self._conv_call(op, ptr, views))
         return calls
+
+    def _conv_call(self, op, ptr, views):
+        """one "conv3" | "down2" | "conv1" op as (name, function, output buffer, arguments)"""
+        L, kind, out = self.hip.lib(), op["kind"], op["out"]
+        packed, scale, shift, cin, cout = self.w[op["conv"]]
+        x, res = op["in"], op["res"]
+        assert (cin, cout) == (x.c, out.c), op["conv"]
+        rptr, rstr = (ptr(res), res.strides) if res is not None else (None, (0, 0, 0, 0))
+        if kind == "conv3":
+            args = [ptr(x), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), rptr, *rstr, 1, ptr(out), views, cin, cout,
+                    x.h, x.w, op["stride"], int(op["relu"]), *out.strides]
+            return ("poem_conv3x3_ex", L.poem_conv3x3_ex, out.buf, args)
+        if kind == "down2":
+            args = [ptr(x), packed.data_ptr(), scale.data_ptr(), shift.data_ptr(), None, ptr(out), views, cin, cout, x.h, x.w,
+                    int(op["relu"]), *out.strides]
+            return ("poem_conv3x3_down2", L.poem_conv3x3_down2, out.buf, args)
+        args = [ptr(x), *x.strides, packed.data_ptr(), shift.data_ptr(), rptr, *rstr, ptr(out), *out.strides, views, cin, cout,
+                x.h, x.w, int(op["relu"])]
+        return ("poem_conv1x1", L.poem_conv1x1, out.buf, args)
 
     def forward(self, x):
         views, H, W = int(x.shape[0]), int(x.shape[-2]), int(x.shape[-1])

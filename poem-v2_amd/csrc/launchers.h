@@ -158,6 +158,18 @@ hipError_t poem_launch_conv1x1_nchw(const float* in, long in_ns, int in_cs, int 
 hipError_t poem_launch_hrnet_fuse(const float* const* ptrs, const long* ns, const int* cs, const int* rs, const int* off,
                                   const int* shift, int nterms, float* out, long out_ns, int out_cs, int out_rs, int out_off,
                                   int views, int C, int H, int W, hipStream_t s);
+// csrc/resnet.hip
+size_t poem_conv7x7_packed_floats(int Cout);
+hipError_t poem_launch_pack_conv7x7(const float* w, int Cout, void* out, hipStream_t s);
+hipError_t poem_launch_conv7x7_s2(const float* in, const void* wp, const float* scale, const float* shift, float* out, long out_ns,
+                                  int out_cs, int out_rs, int out_off, int views, int Cout, int H, int W, hipStream_t s);
+hipError_t poem_launch_maxpool3x3_s2(const float* in, long in_ns, int in_cs, int in_rs, int in_off, float* out, long out_ns,
+                                     int out_cs, int out_rs, int out_off, int views, int C, int H, int W, hipStream_t s);
+hipError_t poem_launch_upcat_pad_staged(const float* a, int Ca, const float* b, int Cb, float* out, int views, int H, int W,
+                                        hipStream_t s);
+hipError_t poem_launch_sconv1x1(const float* in, long in_ns, int in_cs, int in_rs, int in_off, const void* wp, const float* shift,
+                                float* out, long out_ns, int out_cs, int out_rs, int out_off, int views, int Cin, int Cout, int H,
+                                int W, int pool, int act, hipStream_t s);
 hipError_t poem_launch_conv3x3_down2(const float* in, const void* wp, const float* scale, const float* shift, const float* res,
                                      float* out, int views, int Cin, int Cout, int H, int W, int relu, long out_ns, int out_cs,
                                      int out_rs, int out_off, hipStream_t s);

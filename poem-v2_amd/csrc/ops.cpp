@@ -357,6 +357,74 @@ int poem_hrnet_fuse(const poem_fuse_term_t* terms, int nterms, float* out, int64
   return POEM_OK;
 }
 
+// ---- ResNet-18/34/50 and the non-HRNet decode branch (csrc/resnet.hip) ----------------------------------------------------
+size_t poem_conv7x7_packed_bytes(int cout) {
+  if (cout <= 0) return 0;
+  return poem_conv7x7_packed_floats(cout) * sizeof(float);
+}
+
+int poem_pack_conv7x7(const float* w_oihw, int cout, void* packed, void* stream) {
+  if (!w_oihw || !packed || cout <= 0) return POEM_E_ARG;
+  HIPCHK(poem_launch_pack_conv7x7(w_oihw, cout, packed, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+// (H/2) x (W/2) output pixels in whole 32-pixel tiles
+static bool half_tiles(int h, int w) { return h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && ((int64_t)(h / 2) * (w / 2)) % 32 == 0; }
+
+int poem_conv7x7_s2(const float* in, const void* w_packed, const float* scale, const float* shift, float* out,
+                    int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset, int views, int cout, int h, int w,
+                    void* stream) {
+  if (!in || !w_packed || !scale || !shift || !out || views <= 0 || cout <= 0) return POEM_E_ARG;
+  if (!half_tiles(h, w) || cout % 32 || (uint64_t)3 * (uint64_t)h * (uint64_t)w * 4 >= (1ull << 31)) return POEM_E_UNSUPPORTED;
+  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / 2, w / 2)) return POEM_E_ARG;
+  HIPCHK(poem_launch_conv7x7_s2(in, w_packed, scale, shift, out, (long)out_view_stride, out_ch_stride, out_row_stride, out_offset,
+                                views, cout, h, w, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_maxpool3x3_s2(const float* in, int64_t in_view_stride, int in_ch_stride, int in_row_stride, int in_offset, float* out,
+                       int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset, int views, int channels, int h,
+                       int w, void* stream) {
+  if (!in || !out || views <= 0 || channels <= 0) return POEM_E_ARG;
+  if (h <= 0 || w <= 0 || h % 2 || w % 2) return POEM_E_UNSUPPORTED;
+  if (!map_ok(in_view_stride, in_ch_stride, in_row_stride, in_offset, h, w)) return POEM_E_ARG;
+  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / 2, w / 2)) return POEM_E_ARG;
+  if ((int64_t)views * channels * (h / 2) * (w / 2) > (int64_t)0x7fffffff * 256) return POEM_E_UNSUPPORTED;
+  HIPCHK(poem_launch_maxpool3x3_s2(in, (long)in_view_stride, in_ch_stride, in_row_stride, in_offset, out, (long)out_view_stride,
+                                   out_ch_stride, out_row_stride, out_offset, views, channels, h, w, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_conv1x1_s2(const float* in, int64_t in_view_stride, int in_ch_stride, int in_row_stride, int in_offset, const void* w_packed,
+                    const float* shift, float* out, int64_t out_view_stride, int out_ch_stride, int out_row_stride, int out_offset,
+                    int views, int cin, int cout, int h, int w, void* stream) {
+  if (!in || !w_packed || !out || views <= 0 || cin <= 0 || cin % 8 || cout <= 0) return POEM_E_ARG;
+  if (!half_tiles(h, w)) return POEM_E_UNSUPPORTED;
+  if (!map_ok(in_view_stride, in_ch_stride, in_row_stride, in_offset, h, w)) return POEM_E_ARG;
+  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / 2, w / 2)) return POEM_E_ARG;
+  HIPCHK(poem_launch_sconv1x1(in, (long)in_view_stride, in_ch_stride, in_row_stride, in_offset, w_packed, shift, out,
+                              (long)out_view_stride, out_ch_stride, out_row_stride, out_offset, views, cin, cout, h, w, 0, 0,
+                              (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_upsample2_concat_pad_staged(const float* a, int ca, const float* b, int cb, float* out, int views, int h, int w, void* stream) {
+  if (!out || views <= 0 || ca < 0 || cb < 0 || ca + cb <= 0 || (ca && !a) || (cb && !b) || h <= 0 || w <= 0) return POEM_E_ARG;
+  if (ca && (h % 2 || w % 2)) return POEM_E_UNSUPPORTED;
+  HIPCHK(poem_launch_upcat_pad_staged(a, ca, b, cb, out, views, h, w, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+int poem_maxpool2_conv1x1(const float* x, const void* w_packed, const float* bias, float* out, int views, int cin, int cout, int h,
+                          int w, int act, void* stream) {
+  if (!x || !w_packed || !bias || !out || views <= 0 || cin <= 0 || cin % 8 || cout <= 0 || act < 0 || act > 1) return POEM_E_ARG;
+  if (!half_tiles(h, w) || (int64_t)h * w >= (1ll << 31)) return POEM_E_UNSUPPORTED;
+  HIPCHK(poem_launch_sconv1x1(x, (long)cin * h * w, h * w, w, 0, w_packed, bias, out, (long)cout * (h / 2) * (w / 2), (h / 2) * (w / 2),
+                              w / 2, 0, views, cin, cout, h, w, 1, act, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 int poem_conv3x3_down2(const float* in, const void* w_packed, const float* scale, const float* shift, const float* residual,
                        float* out, int views, int cin, int cout, int h, int w, int relu, int64_t out_view_stride,
                        int out_ch_stride, int out_row_stride, int out_offset, void* stream) {

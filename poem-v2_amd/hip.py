@@ -109,6 +109,13 @@ SIGNATURES = {
     "poem_pack_conv1x1": (_i, [_vp, _i, _i, _vp, _vp]),
     "poem_conv1x1": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "poem_hrnet_fuse": (_i, [_vp, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "poem_conv7x7_packed_bytes": (_sz, [_i]),
+    "poem_pack_conv7x7": (_i, [_vp, _i, _vp, _vp]),
+    "poem_conv7x7_s2": (_i, [_vp, _vp, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "poem_maxpool3x3_s2": (_i, [_vp, _i64, _i, _i, _i, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "poem_conv1x1_s2": (_i, [_vp, _i64, _i, _i, _i, _vp, _vp, _vp, _i64, _i, _i, _i, _i, _i, _i, _i, _i, _vp]),
+    "poem_maxpool2_conv1x1": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "poem_upsample2_concat_pad_staged": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _vp]),
     "poem_set_decode_option": (_i, [ctypes.c_char_p, _i]),
     "poem_conv3x3_down2": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp]),
     "poem_upsample2_concat_pad": (_i, [_vp, _i, _vp, _i, _vp, _i, _i, _i, _i, _vp]),

@@ -71,6 +71,15 @@ def synthetic_pyramid(views, seed=0):
     return [torch.randn(views, c, r, r, generator=g) for c, r in zip((40, 80, 160, 320), (64, 32, 16, 8))]
 
 
+def synthetic_resnet_pyramid(channels, views, h, w, seed=0):
+    """ResNet-shaped multi-level features of an h x w image (lib/models/POEM.py:231-237 upstream): (BN,channels[i],h/2^(i+2),
+    w/2^(i+2)), finest first, seeded and non-negative as the ReLU of a block's end leaves them: 0.1 * relu(N(0.3, 1)).  The
+    amplitude keeps the heat-map logits that seeded decode weights make of them inside the sigmoid's unsaturated range, where
+    every pixel of a heat map measures the convolutions in front of it."""
+    g = torch.Generator().manual_seed(8200 + seed)
+    return [0.1 * torch.relu(torch.randn(views, c, h >> (2 + i), w >> (2 + i), generator=g) + 0.3) for i, c in enumerate(channels)]
+
+
 def synthetic_images(views, seed=0, img=256):
     """(BN,3,img,img) seeded N(0, 0.3^2) "images" for the end-to-end timing scope."""
     g = torch.Generator().manual_seed(3000 + seed)

@@ -1,6 +1,6 @@
 """``PtEmbedMultiviewStereoV2`` -- the caller of the hot path, inference side only (lib/models/POEM.py:39-332 upstream):
-images -> HRNet pyramid -> ``feat_decode`` / ``heatmap_stage`` -> ragged DLT -> ``POEM_Generalized_Head`` -> the
-``preds`` dict the reference's ``_forward_impl`` returns (same keys).
+images -> backbone pyramid (HRNet, or ResNet-18 / 34 / 50 by ``BACKBONE.TYPE``) -> ``feat_decode`` / ``heatmap_stage`` -> ragged
+DLT -> ``POEM_Generalized_Head`` -> the ``preds`` dict the reference's ``_forward_impl`` returns (same keys).
 
 Which part runs where: the backbone is plain PyTorch-ROCm (backbone.py; out of the hot path), everything after it is
 the HIP path (decode.py, triangulation.py, head.py -> libpoem_hip.so).  Training-mode noise on the reference joints
@@ -9,14 +9,33 @@ the HIP path (decode.py, triangulation.py, head.py -> libpoem_hip.so).  Training
 import numpy as np
 import torch
 
-from .backbone import HRNet
-from .builder import MODEL, CN, build_head
-from .decode import FeatureDecoders
+from . import resnet  # noqa: F401  (registers ResNet18 / ResNet34 / ResNet50)
+from .backbone import HRNet  # noqa: F401
+from .builder import BACKBONE, MODEL, CN, build_head
+from .decode import FEAT_SIZES, FeatureDecoders
 from .losses import LossMetric, PoemLoss
 from .triangulation import triangulate_reference_joints
 
 
 DLT_CONFIDENCE_MODES = ("off", "threshold", "weighted")
+
+
+def head_in_channels(backbone_name):
+    """channels of the map ``feat_decode`` hands the head: feat_in's output (POEM.py:68-73,94-99) -- 160 / 128 / 512"""
+    f = FEAT_SIZES[backbone_name]
+    return f[2] if backbone_name == "HRNet" else f[1]
+
+
+def build_img_backbone(cfg, device):
+    """``cfg.TYPE`` through the BACKBONE registry (POEM.py:47); a missing node or TYPE means HRNet"""
+    kind = "HRNet" if cfg is None or cfg.get("TYPE", None) is None else cfg.get("TYPE")
+    cls = BACKBONE.get(kind) if isinstance(kind, str) else kind
+    if cls is None:
+        raise KeyError(f"{kind} is not in the {BACKBONE.name} registry")
+    net = cls(cfg, device=device)
+    if getattr(net, "name", None) not in FEAT_SIZES:                      # POEM.py:49
+        raise ValueError(f"backbone {getattr(net, 'name', kind)!r}: the model takes one of {sorted(FEAT_SIZES)}")
+    return net
 
 
 @MODEL.register_module()
@@ -31,8 +50,12 @@ class PtEmbedMultiviewStereoV2:
         preset = cfg.get("DATA_PRESET", CN({}))
         self.center_idx = int(preset.get("CENTER_IDX", 9))                       # POEM.py:50
         self.num_joints = 21
-        self.img_backbone = HRNet(cfg.get("BACKBONE", None), device=self.device)  # POEM.py:57
+        self.img_backbone = build_img_backbone(cfg.get("BACKBONE", None), self.device)   # POEM.py:47
         self.ptEmb_head = build_head(cfg.HEAD, data_preset=preset)                # POEM.py:114
+        want = head_in_channels(self.img_backbone.name)
+        if getattr(self.ptEmb_head, "in_channels", None) is not None and int(self.ptEmb_head.in_channels) != want:
+            raise ValueError(f"HEAD.IN_CHANNELS = {self.ptEmb_head.in_channels}, but the {self.img_backbone.name} backbone's "
+                             f"feat_decode gives the head {want} channels")
         self.num_preds = self.ptEmb_head.num_preds
         # MANO_ASSETS at the model node (the same .npz path as MODEL.HEAD.MANO_ASSETS) reaches the head unless the head's own node
         # names some (head.py: template and MANO layer from them)
@@ -62,7 +85,7 @@ class PtEmbedMultiviewStereoV2:
         of the wrong shape raises.  Returns the keys that were ignored (dead tensors)."""
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}
         ignored = self.img_backbone.load_state_dict(sd, prefix="img_backbone.")
-        self.decoders = FeatureDecoders.load_reference_state_dict(sd, self.device)
+        self.decoders = FeatureDecoders.load_reference_state_dict(sd, self.device, backbone=self.img_backbone.name)
         head_sd = {k[len("ptEmb_head."):]: v for k, v in sd.items() if k.startswith("ptEmb_head.")}
         self.ptEmb_head.load_state_dict(head_sd, strict=strict)
         ignored += ["ptEmb_head." + k for k in self.ptEmb_head.ignored_reference_keys]
@@ -71,7 +94,7 @@ class PtEmbedMultiviewStereoV2:
 
     def load_parts(self, backbone_sd, decoder_sd, head_sd, template=None):
         self.img_backbone.load_state_dict(backbone_sd)
-        self.decoders = FeatureDecoders(decoder_sd, self.device)
+        self.decoders = FeatureDecoders(decoder_sd, self.device, self.img_backbone.name)
         self.ptEmb_head.load_state_dict(head_sd, strict=False)
         if template is not None:
             self.ptEmb_head.set_template(template)

@@ -277,10 +277,11 @@ class StrictLoadFilter:
 _FEAT_SIZE = (40, 80, 160, 320)          # lib/models/POEM.py:55-56 upstream (HRNet)
 
 
-def decoder_key_shapes():
+def decoder_key_shapes(backbone="HRNet"):
     """state_dict keys (relative to the model) and shapes of feat_delayer / feat_in / uv_delayer / uv_out
-    (lib/models/POEM.py:84-112 upstream, HRNet branch)."""
-    f = _FEAT_SIZE
+    (lib/models/POEM.py:59-112 upstream) for the pyramid of ``backbone`` ("HRNet" | "resnet18" | "resnet34" | "resnet50")."""
+    f = {"HRNet": _FEAT_SIZE, "resnet18": (64, 128, 256, 512), "resnet34": (64, 128, 256, 512),
+         "resnet50": (256, 512, 1024, 2048)}[backbone]
     ks = {}
 
     def block(name, cin, cout, k, norm):
@@ -290,6 +291,13 @@ def decoder_key_shapes():
             for n in ("weight", "bias", "running_mean", "running_var"):
                 ks[f"{name}.norm.{n}"] = (cout,)
 
+    if backbone != "HRNet":                                  # POEM.py:59-86: both stacks go up from the coarsest level
+        for stack in ("feat_delayer", "uv_delayer"):
+            for i in range(3):
+                block(f"{stack}.{i}", f[3 - i] + f[2 - i], f[2 - i], 3, True)
+        block("feat_in", f[0], f[1], 1, False)
+        block("uv_out", f[0], 21, 1, False)
+        return ks
     for i in range(3):
         block(f"feat_delayer.{i}", f[i], f[i + 1], 3, True)
     block("feat_in", f[3], f[2], 1, False)
@@ -300,14 +308,14 @@ def decoder_key_shapes():
     return ks
 
 
-def seeded_decoder_state_dict(seed=0):
+def seeded_decoder_state_dict(seed=0, backbone="HRNet"):
     """Deterministic weights for fixtures / benches: conv weights N(0, sqrt(2 / fan_out)) as ConvBlock's
     kaiming_normal_(mode='fan_out') draws them (lib/models/bricks/conv.py:31-33 upstream), small random biases, and
     *non-trivial* BatchNorm statistics so that the folded affine is exercised (the reference initialises gamma = 1,
     beta = 0, mean = 0, var = 1)."""
     g = torch.Generator().manual_seed(1000 + seed)
     sd = {}
-    for k, shp in decoder_key_shapes().items():
+    for k, shp in decoder_key_shapes(backbone).items():
         if k.endswith("conv.weight"):
             fan_out = shp[0] * shp[2] * shp[3]
             sd[k] = torch.randn(shp, generator=g) * (2.0 / fan_out) ** 0.5

@@ -250,15 +250,19 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
     return res
 
 
+BACKBONE_TYPES = {"hrnet": "HRNet", "resnet18": "ResNet18", "resnet34": "ResNet34", "resnet50": "ResNet50"}
+
+
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
                     n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
-                    mano_assets=None, backbone_engine="torch"):
+                    mano_assets=None, backbone_engine="torch", backbone="hrnet"):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
     (``PtEmbedMultiviewStereoV2``: HRNet on PyTorch-ROCm -> decode / heat maps / DLT / head on HIP) and the device metrics
     against the records' ``master_joints_3d`` / ``master_verts_3d`` (lib/models/POEM.py:596-610 upstream).
-    ``backbone_engine``: ``"hip"`` runs HRNet on the project's own convolution kernels (model key BACKBONE.ENGINE).
+    ``backbone_engine``: ``"hip"`` runs the backbone on the project's own convolution kernels (model key BACKBONE.ENGINE).
+    ``backbone``: "hrnet" | "resnet18" | "resnet34" | "resnet50" sets MODEL.BACKBONE.TYPE and MODEL.HEAD.IN_CHANNELS (160 / 128 / 512).
     ``losses``: MANO's (16,778) joint regressor (``--losses --j-regressor``): every batch's loss terms (upstream's ``compute_loss``,
     value only) feed the model's ``loss_metric`` on the device and the result gains their batch-size-weighted averages.
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
@@ -286,6 +290,10 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         model_node["MANO_ASSETS"] = mano_assets
     if backbone_engine != "torch":
         model_node["BACKBONE"] = {"ENGINE": backbone_engine}
+    if backbone != "hrnet":
+        kind = BACKBONE_TYPES[backbone]
+        model_node["BACKBONE"] = dict(model_node.get("BACKBONE", {}), TYPE=kind, PRETRAINED=False, FREEZE_BATCHNORM=True)
+        head_node["IN_CHANNELS"] = pk.model.head_in_channels(pk.BACKBONE.get(kind)().name)
     model = pk.build_model(pk.CN(model_node))
     if losses is not None:
         model.set_j_regressor(losses)
@@ -296,8 +304,11 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     else:
         template_source = f"file:{template}" if template else f"mano-assets:{mano_assets}" if mano_assets else "synthetic(seed=1234)"
         from poem_v2_amd.backbone import seeded_hrnet_state_dict
-        model.load_parts(seeded_hrnet_state_dict(0), pk.weights.seeded_decoder_state_dict(0),
-                         pk.weights.seeded_state_dict(model.ptEmb_head.embed_dims, seed=0,
+        from poem_v2_amd.resnet import seeded_resnet_state_dict
+        net = model.img_backbone
+        model.load_parts(seeded_hrnet_state_dict(0) if net.name == "HRNet" else seeded_resnet_state_dict(net.version, 0),
+                         pk.weights.seeded_decoder_state_dict(0, backbone=net.name),
+                         pk.weights.seeded_state_dict(model.ptEmb_head.embed_dims, seed=0, in_channels=model.ptEmb_head.in_channels,
                                                       parametric=model.ptEmb_head.parametric_output),
                          template=load_template(template) if template else None if mano_assets
                          else pk.inputs.synthetic_template(1234))
@@ -397,7 +408,8 @@ def main(args):
                               epoch_size=args.epoch_size, batch_size=args.batch_size, template=args.template,
                               dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw,
                               losses=j_regressor, mano_assets=mano_assets,
-                              backbone_engine=getattr(args, "backbone_engine", "torch"))
+                              backbone_engine=getattr(args, "backbone_engine", "torch"),
+                              backbone=getattr(args, "backbone", "hrnet"))
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
@@ -463,6 +475,9 @@ def build_cli():
     parser.add_argument("--backbone-engine", choices=("torch", "hip"), default=argparse.SUPPRESS,
                         help="with --shards: what runs HRNet-W40 -- torch (PyTorch-ROCm / MIOpen, the default) or hip (the project's own "
                              "gfx950 convolution kernels; model key BACKBONE.ENGINE).  The other scopes start behind the backbone.")
+    parser.add_argument("--backbone", choices=tuple(BACKBONE_TYPES), default=argparse.SUPPRESS,
+                        help="with --shards: the image backbone (default hrnet); sets MODEL.BACKBONE.TYPE and MODEL.HEAD.IN_CHANNELS "
+                             "(160 / 128 / 512).")
     return parser
 
 

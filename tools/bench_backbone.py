@@ -1,9 +1,10 @@
 #!/usr/bin/env python
-"""HRNet-W40 forward time on one GPU: ``--engine torch`` (PyTorch-ROCm / MIOpen) or ``--engine hip`` (the project's own
-convolution kernels, poem_v2_amd/backbone.py).  Prints one JSON line: per-forward median / min / max over ``--steps`` timed
-forwards (device events around each), images/s, and the fraction of the fp32 matrix peak from the FLOP count of
-``backbone._conv_specs`` at this input size.  ``--miopen-ab``: the older A/B of the torch engine's memory format and MIOpen
-find mode."""
+"""Backbone forward time on one GPU: ``--backbone hrnet`` (HRNet-W40, the default) | ``resnet18`` | ``resnet34`` | ``resnet50``
+on ``--engine torch`` (PyTorch-ROCm / MIOpen) or ``--engine hip`` (the project's own convolution kernels, poem_v2_amd/backbone.py
+and resnet.py).  Prints one JSON line per engine named: per-forward median / min / max over ``--steps`` timed forwards (device
+events around each), images/s, and the fraction of the fp32 matrix peak from the FLOP count of the backbone's ``_conv_specs`` at
+this input size.  Several engines (``--engine torch hip torch``) run one after the other in this process, each on a model of its
+own: an A/B/A of one session.  ``--miopen-ab``: the older A/B of the torch engine's memory format and MIOpen find mode."""
 import argparse
 import json
 import os
@@ -16,6 +17,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 import poem_v2_amd as pk  # noqa: E402,F401
+from poem_v2_amd import resnet  # noqa: E402
 from poem_v2_amd.backbone import HipPlan, HRNet, seeded_hrnet_state_dict  # noqa: E402
 
 FP32_MATRIX_PEAK = 157.3e12
@@ -30,6 +32,31 @@ def hrnet_flops(H, W):
             cin = 3 if op["conv"] == "conv1" else op["in"].c
             total += 2 * k * k * cin * op["out"].c * op["out"].h * op["out"].w
     return total
+
+
+def resnet_flops(version, H, W):
+    """multiply-adds x 2 of every convolution of ``resnet._conv_specs``, per view, and of the 7x7 stem alone"""
+    total, stem, h, w = 0, 0, H, W
+    for name, _, cout, cin, k, stride in resnet._conv_specs(version):
+        if name.endswith("downsample.0"):                       # reads what the block's strided convolution read
+            flops = 2 * cin * cout * (h_in // stride) * (w_in // stride)
+        else:
+            h_in, w_in = h, w
+            h, w = h // stride, w // stride
+            flops = 2 * k * k * cin * cout * h * w
+        if name == "conv1":
+            stem = flops
+            h, w = h // 2, w // 2                                # the 3x3 stride-2 max-pool
+        total += flops
+    return total, stem
+
+
+def build(backbone, engine, dev):
+    if backbone == "hrnet":
+        return HRNet({"ENGINE": engine}, state_dict=seeded_hrnet_state_dict(0), device=dev)
+    version = int(backbone[len("resnet"):])
+    cls = {18: resnet.ResNet18, 34: resnet.ResNet34, 50: resnet.ResNet50}[version]
+    return cls({"ENGINE": engine}, state_dict=resnet.seeded_resnet_state_dict(version, 0), device=dev)
 
 
 def miopen_ab(views, dev):
@@ -61,7 +88,8 @@ def miopen_ab(views, dev):
 def main():
     ap = argparse.ArgumentParser(description=__doc__)
     ap.add_argument("views", type=int, nargs="?", default=256)
-    ap.add_argument("--engine", choices=("torch", "hip"), default="torch")
+    ap.add_argument("--engine", choices=("torch", "hip"), nargs="+", default=["torch"])
+    ap.add_argument("--backbone", choices=("hrnet", "resnet18", "resnet34", "resnet50"), default="hrnet")
     ap.add_argument("--size", type=int, nargs=2, default=(256, 256), metavar=("H", "W"))
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
@@ -72,25 +100,34 @@ def main():
         return miopen_ab(a.views, dev)
     H, W = a.size
     img = (0.5 * torch.randn(a.views, 3, H, W, generator=torch.Generator().manual_seed(1))).to(dev)
-    net = HRNet({"ENGINE": a.engine}, state_dict=seeded_hrnet_state_dict(0), device=dev)
-    for _ in range(a.warmup):
-        ys = net(img)
-    torch.cuda.synchronize()
-    times = []
-    for _ in range(a.steps):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        ys = net(img)
-        e1.record()
-        e1.synchronize()
-        times.append(e0.elapsed_time(e1))
-    med = statistics.median(times)
-    flops = hrnet_flops(H, W) * a.views
-    print(json.dumps({"engine": a.engine, "views": a.views, "size": [H, W], "steps": a.steps, "ms_median": round(med, 3),
-                      "ms_min": round(min(times), 3), "ms_max": round(max(times), 3), "images_per_s": round(a.views / med * 1e3, 1),
-                      "gflop_per_view": round(flops / a.views / 1e9, 2), "tflops": round(flops / med / 1e9, 2),
-                      "fp32_matrix_peak_fraction": round(flops / (med * 1e-3) / FP32_MATRIX_PEAK, 4),
-                      "checksum": float(sum(y.double().abs().mean() for y in ys))}))
+    extra = {}
+    if a.backbone == "hrnet":
+        flops = hrnet_flops(H, W) * a.views
+    else:
+        per_view, stem = resnet_flops(int(a.backbone[len("resnet"):]), H, W)
+        flops, extra = per_view * a.views, {"stem_gflop": round(stem * a.views / 1e9, 2)}
+    for engine in a.engine:
+        net = build(a.backbone, engine, dev)
+        for _ in range(a.warmup):
+            ys = net(img)
+        torch.cuda.synchronize()
+        times = []
+        for _ in range(a.steps):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            ys = net(img)
+            e1.record()
+            e1.synchronize()
+            times.append(e0.elapsed_time(e1))
+        med = statistics.median(times)
+        print(json.dumps({"backbone": a.backbone, "engine": engine, "views": a.views, "size": [H, W], "steps": a.steps,
+                          "ms_median": round(med, 3), "ms_min": round(min(times), 3), "ms_max": round(max(times), 3),
+                          "images_per_s": round(a.views / med * 1e3, 1), "gflop_per_view": round(flops / a.views / 1e9, 2),
+                          "tflops": round(flops / med / 1e9, 2),
+                          "fp32_matrix_peak_fraction": round(flops / (med * 1e-3) / FP32_MATRIX_PEAK, 4),
+                          "checksum": float(sum(y.double().abs().mean() for y in ys)), **extra}), flush=True)
+        del net, ys
+        torch.cuda.empty_cache()
 
 
 if __name__ == "__main__":
