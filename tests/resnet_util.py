@@ -10,6 +10,7 @@ import torch.nn.functional as F
 
 import decode_oracle as do
 from poem_v2_amd import resnet as rn
+from poem_v2_amd.backbone import run_graph
 from poem_v2_amd.decode import FEAT_SIZES
 from poem_v2_amd.inputs import synthetic_resnet_pyramid
 
@@ -50,16 +51,8 @@ def net_in(version, sd, dtype=torch.float32):
 
 
 def cpu_forward(net, x):
-    """resnet._ResNet.forward's torch branch in the dtype of ``x`` (the class's own forward casts to fp32)"""
-    with torch.no_grad():
-        x = net._convs["conv1"](x, relu=True)
-        x = F.max_pool2d(x, kernel_size=3, stride=2, padding=1)
-        levels = []
-        for L, nblocks in enumerate(rn.VERSIONS[net.version][1], start=1):
-            for b in range(nblocks):
-                x = net._block(f"layer{L}.{b}", x)
-            levels.append(x)
-    return levels
+    """the torch engine's forward (backbone.run_graph) in the dtype of ``x`` (the class's own forward casts to fp32)"""
+    return run_graph(net._graph, net._convs, x)
 
 
 def criterion(got, ref64, ref32, what=""):

@@ -1,5 +1,6 @@
 """End-to-end scope plumbing (SURVEY 8d "E2E"): the PyTorch HRNet-W40 backbone pinned to the reference's own HRNet
 (CPU), and the model-level caller ``PtEmbedMultiviewStereoV2`` from images to the preds dict (GPU)."""
+import hashlib
 import json
 import os
 
@@ -38,6 +39,15 @@ def test_hrnet_key_table_and_prefix_loading():
     assert shapes["transition1.1.0.0.weight"] == (80, 256, 3, 3) and shapes["transition3.3.0.0.weight"] == (320, 160, 3, 3)
     assert shapes["stage4.2.fuse_layers.3.0.2.0.weight"] == (320, 40, 3, 3)
     assert shapes["stage3.1.fuse_layers.0.2.0.weight"] == (40, 160, 1, 1)
+    # the table and the seeded weights the fixtures hang on, as recorded when the table was written out by hand
+    specs = bb._conv_specs()
+    assert (len(specs), hashlib.sha256(repr(specs).encode()).hexdigest()) == (
+        305, "6a782c18c4d1dbd4840e241e245c189995be6b253a29c96837b9ae6ed58a1c88")
+    h, seeded = hashlib.sha256(), bb.seeded_hrnet_state_dict(0)
+    for key, tensor in seeded.items():
+        h.update(key.encode())
+        h.update(tensor.numpy().tobytes())
+    assert (len(seeded), h.hexdigest()) == (1525, "4ea67820bb6f5aa722f7223b0a1c7b95497d8432fef8d49bedf6abb461252b25")
     sd = {"img_backbone." + k: v for k, v in bb.seeded_hrnet_state_dict(1).items()}
     sd["img_backbone.classifier.weight"] = torch.zeros(1000, 2048)          # dead head: ignored, reported
     net = bb.HRNet()

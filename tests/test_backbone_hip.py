@@ -285,18 +285,8 @@ def test_hrnet_fuse_refusals():
 
 # ---- the whole backbone -------------------------------------------------------------------------------------------------
 def _cpu_forward(net, x):
-    """the torch engine's forward (backbone.HRNet.forward) in the dtype of ``x`` and of the net's folded weights"""
-    c = net._convs
-    x = c["conv1"](x, relu=True)
-    x = c["conv2"](x, relu=True)
-    for i in range(4):
-        x = net._bottleneck(f"layer1.{i}", x)
-    ys = [x]
-    for s, (nb, nm) in enumerate(bb.STAGES, start=1):
-        ys = net._transition(s, ys, nb)
-        for m in range(nm):
-            ys = net._module(f"stage{s + 1}.{m}", ys)
-    return ys
+    """the torch engine's forward (backbone.run_graph) in the dtype of ``x`` and of the net's folded weights"""
+    return bb.run_graph(net._graph, net._convs, x)
 
 
 @pytest.fixture(scope="module")

@@ -30,6 +30,25 @@ def _npz(name):
 
 
 # ---- key tables and loading ---------------------------------------------------------------------------------------------
+KEY_TABLES_AS_THEY_WERE = {  # version -> rows and sha256 of repr(_conv_specs), tensors and digest of the seed-0 weights
+    18: (20, "b79f47db096b38b5cc8879a6fabb185f799f3520e9d6662447fb4ee42827d89d",
+         100, "58c325cec6c3fbe9ce580bd88f419db35253ccc15c4b4e67dcc26073d991fccb"),
+    34: (36, "cc387e02acb0110d7e7306e80cd2f89eefbaa17137ee2970979496d18a29a3c7",
+         180, "b8250e351ba4636f4ad3c04a5e7dd58f6022df89f9c6de2ced14710404425478"),
+    50: (53, "e0c0a3819e3561711e37284697786ec44917f2d364195c935424cc8bc0515645",
+         265, "d187529c7be53279fd45a7230acd2f518716b16a447d1952c42cb7212d8244ed"),
+}
+
+
+def state_dict_digest(sd):
+    """(tensor count, sha256 over key then bytes of every item in dict order)"""
+    h = hashlib.sha256()
+    for key, tensor in sd.items():
+        h.update(key.encode())
+        h.update(tensor.numpy().tobytes())
+    return len(sd), h.hexdigest()
+
+
 @pytest.mark.parametrize("version", ru.VERSIONS)
 def test_key_tables_are_the_reference_models(version):
     table = _keys()[f"resnet{version}"]
@@ -39,6 +58,11 @@ def test_key_tables_are_the_reference_models(version):
     dead = [k for k in ref if k not in live]
     assert "fc.weight" in dead and "fc.bias" in dead and all(k.startswith("fc.") or k.endswith(".num_batches_tracked") for k in dead)
     assert sorted(f"{s[0]}.weight" for s in rn._conv_specs(version)) == sorted(k for k in live if len(live[k]) == 4)
+    # the table and the seeded weights the fixtures hang on, as recorded when the table was written out by hand
+    rows, specs_sha, tensors, seeded_sha = KEY_TABLES_AS_THEY_WERE[version]
+    specs = rn._conv_specs(version)
+    assert (len(specs), hashlib.sha256(repr(specs).encode()).hexdigest()) == (rows, specs_sha)
+    assert state_dict_digest(rn.seeded_resnet_state_dict(version, 0)) == (tensors, seeded_sha)
     # the decode stage: the same keys for every backbone, the channel table by the backbone's name
     name = f"resnet{version}"
     dec = {k: tuple(s) for k, s in table["decode"].items() if not k.startswith("uv_in.") and not k.endswith(".num_batches_tracked")}
@@ -187,13 +211,32 @@ def plan_digest(plan):
         if op["kind"] == "fuse":
             rows.append(("fuse", "", g(op["out"]), tuple((g(m), s) for m, s in op["terms"])))
         else:
-            rows.append((op["kind"], op.get("conv", ""), g(op["out"]), g(op.get("in")), g(op.get("res"))))
+            rows.append((op["kind"], op.get("conv", ""), g(op.get("out")), g(op.get("in")), g(op.get("res"))))
     return len(rows), hashlib.sha256(repr(rows).encode()).hexdigest()
 
 
-def test_hrnet_plan_is_what_it_was():
-    """recorded from the commit before the ResNet engine shared HipPlan's helpers"""
-    assert plan_digest(bb.HipPlan(3, 128, 256)) == (332, "ab45289f3b6921991096f987c8f0a98be72d6865a9f89d9beb1b57e55b0f490d")
+PLANS_AS_THEY_WERE = [  # plan, its arguments, (ops, sha256), buffers, nbytes
+    ("hrnet", (3, 128, 256), (332, "ab45289f3b6921991096f987c8f0a98be72d6865a9f89d9beb1b57e55b0f490d"), 35, 43319040),
+    ("hrnet", (1, 256, 256), (332, "f1ee9c511077331a3dfe076ebb0039f78821aea60b71169196f86085c6ace03b"), 33, 28169088),
+    ("hrnet", (2, 512, 512), (332, "85b750a7c5ea5a8dd1c5d3b2031e82096ed6efbd12ef7c48ef51e0d862781f23"), 35, 222234112),
+    ("resnet", (2, 128, 256, 18), (25, "cea32ca7282492b332c4cd6cc7847aaa73ead0bdcf9d8514d0cf8ad100802bc3"), 15, 12036096),
+    ("resnet", (1, 256, 256, 18), (25, "e1d8d32a3dfefd54ffede069cd2ce271ca8dbc8d2e4190f3b48bb399b019f45b"), 15, 11637760),
+    ("resnet", (2, 128, 256, 34), (41, "f22aaae4724ebecb805e294d3e1467e99a62b3dc63d903cca30827c7cfb2d410"), 16, 12281856),
+    ("resnet", (1, 256, 256, 34), (41, "57e1f4b70d070ff43f8cfa0764d70924811c2af33a275b273130538b83a409d1"), 16, 11842560),
+    ("resnet", (2, 128, 256, 50), (58, "4b087fa8e09ba6211f6dca6810b915e7a950fa08094b40657c35dde66d321df4"), 21, 29616128),
+    ("resnet", (1, 256, 256, 50), (58, "b6d64878918cb59c6b989b789664c17fec245c364712b8ed9d04de5250365c21"), 21, 29258752),
+]
+
+
+@pytest.mark.parametrize("family,args,digest,buffers,nbytes", PLANS_AS_THEY_WERE,
+                         ids=[f"{row[0]}-{'x'.join(map(str, row[1]))}" for row in PLANS_AS_THEY_WERE])
+def test_plan_is_what_it_was(family, args, digest, buffers, nbytes):
+    """recorded from the commits in which the plans were written out by hand: the first row before the ResNet engine shared
+    HipPlan's helpers, the others before both plans were derived from the networks' descriptions"""
+    plan = {"hrnet": bb.HipPlan, "resnet": rn.ResNetPlan}[family](*args)
+    assert plan_digest(plan) == digest
+    print(f"{family} {args}: {len(plan.buffers)} buffers, {plan.nbytes()} bytes")
+    assert len(plan.buffers) <= buffers and plan.nbytes() <= nbytes
 
 
 @pytest.mark.parametrize("version", ru.VERSIONS)

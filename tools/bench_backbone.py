@@ -2,7 +2,7 @@
 """Backbone forward time on one GPU: ``--backbone hrnet`` (HRNet-W40, the default) | ``resnet18`` | ``resnet34`` | ``resnet50``
 on ``--engine torch`` (PyTorch-ROCm / MIOpen) or ``--engine hip`` (the project's own convolution kernels, poem_v2_amd/backbone.py
 and resnet.py).  Prints one JSON line per engine named: per-forward median / min / max over ``--steps`` timed forwards (device
-events around each), images/s, and the fraction of the fp32 matrix peak from the FLOP count of the backbone's ``_conv_specs`` at
+events around each), images/s, and the fraction of the fp32 matrix peak from the FLOP count of the backbone's description at
 this input size.  Several engines (``--engine torch hip torch``) run one after the other in this process, each on a model of its
 own: an A/B/A of one session.  ``--miopen-ab``: the older A/B of the torch engine's memory format and MIOpen find mode."""
 import argparse
@@ -18,36 +18,20 @@ import torch  # noqa: E402
 
 import poem_v2_amd as pk  # noqa: E402,F401
 from poem_v2_amd import resnet  # noqa: E402
-from poem_v2_amd.backbone import HipPlan, HRNet, seeded_hrnet_state_dict  # noqa: E402
+from poem_v2_amd.backbone import Graph, HRNet, hrnet, seeded_hrnet_state_dict  # noqa: E402
 
 FP32_MATRIX_PEAK = 157.3e12
 
 
-def hrnet_flops(H, W):
-    """multiply-adds x 2 of every convolution, per view (the padded stem channels are not counted)"""
-    total = 0
-    for op in HipPlan(1, H, W).ops:
-        if "conv" in op:
-            k = 1 if op["kind"] == "conv1" else 3
-            cin = 3 if op["conv"] == "conv1" else op["in"].c
-            total += 2 * k * k * cin * op["out"].c * op["out"].h * op["out"].w
-    return total
-
-
-def resnet_flops(version, H, W):
-    """multiply-adds x 2 of every convolution of ``resnet._conv_specs``, per view, and of the 7x7 stem alone"""
-    total, stem, h, w = 0, 0, H, W
-    for name, _, cout, cin, k, stride in resnet._conv_specs(version):
-        if name.endswith("downsample.0"):                       # reads what the block's strided convolution read
-            flops = 2 * cin * cout * (h_in // stride) * (w_in // stride)
-        else:
-            h_in, w_in = h, w
-            h, w = h // stride, w // stride
-            flops = 2 * k * k * cin * cout * h * w
-        if name == "conv1":
-            stem = flops
-            h, w = h // 2, w // 2                                # the 3x3 stride-2 max-pool
-        total += flops
+def conv_flops(graph, H, W):
+    """multiply-adds x 2 of every convolution of a description, per view (the image's 3 channels, not the padded ones), and of
+    a 7x7 stem alone"""
+    total = stem = 0
+    for n in graph.nodes:
+        if n.op == "conv":
+            flops = 2 * n.k * n.k * n.x.c * n.out.c * (H >> n.out.down) * (W >> n.out.down)
+            total += flops
+            stem += flops if n.k == 7 else 0
     return total, stem
 
 
@@ -101,11 +85,11 @@ def main():
     H, W = a.size
     img = (0.5 * torch.randn(a.views, 3, H, W, generator=torch.Generator().manual_seed(1))).to(dev)
     extra = {}
-    if a.backbone == "hrnet":
-        flops = hrnet_flops(H, W) * a.views
-    else:
-        per_view, stem = resnet_flops(int(a.backbone[len("resnet"):]), H, W)
-        flops, extra = per_view * a.views, {"stem_gflop": round(stem * a.views / 1e9, 2)}
+    graph = Graph(hrnet) if a.backbone == "hrnet" else Graph(resnet.resnet, int(a.backbone[len("resnet"):]))
+    per_view, stem = conv_flops(graph, H, W)
+    flops = per_view * a.views
+    if stem:
+        extra = {"stem_gflop": round(stem * a.views / 1e9, 2)}
     for engine in a.engine:
         net = build(a.backbone, engine, dev)
         for _ in range(a.warmup):
