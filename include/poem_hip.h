@@ -392,12 +392,13 @@ int poem_dlt_confidence(const float* uv, const float* conf, const float* cam_int
  *   BatchNorm folded by the caller; arrays padded to a multiple of 32 channels), optional ReLU, optional lateral add
  *   residual (views,cout,h/stride,w/stride) AFTER the activation (POEM.py:185-186); element (n,c,y,x) is written to
  *   out[n*out_view_stride + c*out_ch_stride + y*out_row_stride + x + out_offset] so that the result can land inside
- *   the next conv's zero-bordered input.  stride 1|2 (padding 1), (h/stride)*(w/stride) % 32 == 0.
+ *   the next conv's zero-bordered input.  stride 1|2 (padding 1), (h/stride)*(w/stride) % 32 == 0.  The ReLU is torch's: a NaN
+ *   stays a NaN (compare + select, not a max) -- here and in every operator of this block that takes `relu`.
  * poem_upsample2_concat_pad: out (views, ca+cb, h+2*pad, w+2*pad) = [bilinear x2 (align_corners=False) of
  *   a (views,ca,h/2,w/2) | b (views,cb,h,w)] with a zero border of pad (0|1) pixels (F.interpolate + torch.cat,
  *   POEM.py:189,203-204); ca or cb may be 0.
  * poem_pool_conv1x1_sigmoid: x (views,c,h,w) -> max_pool2d(2,2) -> 1x1 conv (j x c, bias) -> sigmoid ->
- *   heatmaps (views,j,h/2,w/2)  (POEM.py:206-207); c <= 64, j <= 32. */
+ *   heatmaps (views,j,h/2,w/2)  (POEM.py:206-207); c <= 64, j <= 32.  The maximum is max_pool2d's: NaN if any of the four is. */
 size_t poem_conv3x3_packed_bytes(int cout, int cin);
 int poem_pack_conv3x3(const float* w_oihw, int cout, int cin, void* packed, void* stream);
 int poem_conv3x3(const float* in_padded, const void* w_packed, const float* scale, const float* shift,
@@ -505,8 +506,9 @@ int poem_conv1x1_upsample2(const float* in, const void* w_packed, const float* b
 /* One uv_decode stage in one launch (POEM.py:203-205: F.interpolate x2, torch.cat, ConvBlock): stride-1 conv3x3 of
  * [bilinear x2 of a_half (views,ca,h/2,w/2) | b_full (views,cb,h,w)] with the concatenation, the zero border and the
  * upsampling applied while the input halo is staged in LDS -- the concatenated tensor never exists.  Same epilogue and output
- * addressing as poem_conv3x3.  POEM_E_UNSUPPORTED for shapes the LDS-staged kernel does not take (cout > 160, w > 64,
- * 256 % w != 0, ...): call poem_upsample2_concat_pad + poem_conv3x3 then. */
+ * addressing as poem_conv3x3.  The border is zero whatever a_half holds (a select, not a product with zero tap weights: a NaN or
+ * Inf in a_half reaches the outputs F.interpolate + the convolution would give it, no others).  POEM_E_UNSUPPORTED for shapes the
+ * LDS-staged kernel does not take (cout > 160, w > 64, 256 % w != 0, ...): call poem_upsample2_concat_pad + poem_conv3x3 then. */
 int poem_upcat_conv3x3(const float* a_half, int ca, const float* b_full, int cb, const void* w_packed, const float* scale,
                        const float* shift, float* out, int views, int cout, int h, int w, int relu, int64_t out_view_stride,
                        int out_ch_stride, int out_row_stride, int out_offset, void* stream);
@@ -516,8 +518,10 @@ int poem_pool_conv1x1_sigmoid(const float* x, const float* w, const float* bias,
  * then max_pool2d(2, 2) + uv_out + sigmoid): poem_upcat_conv3x3 whose epilogue pools its own rows, contracts them with
  * head_w (j x cout, row-major) + head_b and writes sigmoid(.) to heatmaps (views, j, h/2, w/2) -- the convolution's
  * (views, cout, h, w) output, which nothing else reads, never reaches HBM.  Same bits as poem_upcat_conv3x3 +
- * poem_pool_conv1x1_sigmoid.  POEM_E_UNSUPPORTED unless w == 64, 33 <= cout <= 48, j <= 32 and ca, cb are multiples of 8:
- * call the two operators then. */
+ * poem_pool_conv1x1_sigmoid, NaN and Inf inputs included (the same NaN-keeping ReLU and maxima in the same order).
+ * POEM_E_UNSUPPORTED unless w == 64, h % 4 == 0, 33 <= cout <= 48, 1 <= j <= 32, ca, cb positive multiples of 8 and the pooled rows
+ * and head weights fit the staging tile ((128 cout + j cout + j) floats <= 6400: j <= 31 at cout 40, j <= 5 at cout 48): call the
+ * two operators then. */
 int poem_upcat_conv3x3_pool_head(const float* a_half, int ca, const float* b_full, int cb, const void* w_packed, const float* scale,
                                  const float* shift, const float* head_w, const float* head_b, float* heatmaps, int views, int cout,
                                  int j, int h, int w, int relu, void* stream);

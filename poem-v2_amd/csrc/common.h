@@ -96,6 +96,9 @@ __device__ __forceinline__ float4 frag_load(__amdgpu_buffer_rsrc_t rs, int lane_
 // Linear epilogues between the sampled features and the coordinate update, not inside the vector attention (whose values carry
 // the NaN past its own ReLUs).
 __device__ __forceinline__ float relu_nan(float v) { return v < 0.f ? 0.f : v; }
+// max as torch's max_pool2d evaluates it: NaN if either operand is (fmaxf returns the other one).  Compare + select; both 2x2
+// max-pools of decode.hip take their maxima through it, in the same order, so their results stay the same bits.
+__device__ __forceinline__ float max_nan(float a, float b) { return (a > b || a != a) ? a : b; }
 
 __device__ __forceinline__ float gelu_erf(float x) { return x * 0.5f * (1.0f + erff(x * 0.70710678118654752440f)); }
 

@@ -114,7 +114,7 @@ __device__ __forceinline__ float conv3_ex_tail(const Conv3Args& A, int n, int co
     if (A.res) v += r;
     if (A.relu) v = relu_nan(v);
   } else {
-    if (A.relu) v = fmaxf(v, 0.f);
+    if (A.relu) v = relu_nan(v);
     if (A.res) v += r;
   }
   return v;
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args A) {
           float v = fmaf(acc[c][p][4 * g + e], (&sc.x)[e], (&sh.x)[e]);
           if constexpr (EX) v = conv3_ex_tail(A, n, co, py[p], px[p], v);
           else {
-            if (A.relu) v = fmaxf(v, 0.f);
+            if (A.relu) v = relu_nan(v);
             if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + py[p] * Wo + px[p]];
           }
           A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + py[p] * A.out_rs + px[p] + A.out_off] = v;
@@ -215,8 +215,9 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args A) {
 // Staging of one 8-channel chunk of a convolution's input tile -- (TR + 2) x (W + 2) per channel, zero border included --
 // into LDS, shared by the LDS-staged kernels below.  Per staged float everything that does not depend on the chunk is
 // worked out once (init): its LDS slot, and for the plain input its byte offset; for the fused [bilinear x2 of up_a | skip_b]
-// input the four tap offsets and the four tap weights of F.interpolate(scale_factor=2, align_corners=False) -- the weights
-// of an out-of-image position are zero, so the border costs no select -- or the skip tensor's offset.  The chunk's part of
+// input the four tap offsets and the four tap weights of F.interpolate(scale_factor=2, align_corners=False) -- an
+// out-of-image position is a select on the result (zero weights alone would make 0 * NaN of whatever its taps read: a NaN or
+// Inf at pixel (0, 0) of a chunk's first channel poisoned the whole border) -- or the skip tensor's offset.  The chunk's part of
 // every address is a scalar offset of a per-view buffer descriptor: `load` is loads only (no VALU), `finish` one multiply and
 // three fmas per interpolated float.  (Round 2 unpacked bit fields and formed 64-bit addresses per float and chunk: a fifth of
 // the fused kernels' time went into staging arithmetic that the fp32 MFMAs do not overlap with.)
@@ -318,7 +319,7 @@ struct Conv3Stager {
     if (!UPCAT) return;
 #pragma unroll
     for (int u = 0; u < MAXLD; ++u)
-      st[u] = KIND == 2 ? fmaf(q3[u], r3[u], fmaf(q2[u], r2[u], fmaf(q1[u], r1[u], q0[u] * st[u]))) : (ob[u] >= 0 ? st[u] : 0.f);
+      st[u] = ob[u] < 0 ? 0.f : KIND == 2 ? fmaf(q3[u], r3[u], fmaf(q2[u], r2[u], fmaf(q1[u], r1[u], q0[u] * st[u]))) : st[u];
   }
   __device__ __forceinline__ void store(float* buf, int tid, int nthreads = 512) const {
 #pragma unroll
@@ -332,8 +333,10 @@ struct Conv3Stager {
 // of the chunk, a lane one image column of some of the tile's rows.  A lane's column pair (xx0, xx1) and its weights (hx, lx)
 // never change; tile row r (image row y0 - 1 + r) interpolates between the source rows (L_{r/2}, L_{r/2+1}) of the TR / 2 + 2
 // rows L_i = clamp(y0 / 2 - 1 + i) the tile needs, with the row weight ly of F.interpolate's own formula (wave-uniform at
-// W = 64; hy = 1 - ly; both 0 outside the image).  At the top edge the formula's second source row differs from the pattern's,
-// with weight ly = 0 there: the value is the same.  8 / 12 coalesced row loads per chunk instead of 28 scattered taps, and ~20
+// W = 64; hy = 1 - ly; a row outside the image is zero by a select).  Image row 0 is the one row the pattern does not fit: the
+// formula's pair is (0, 1) with ly = 0 where the pattern's is (L_0, L_1) = (0, 0) -- the same value, unless source row 0 holds an
+// Inf (0 * Inf where the formula has 0 * row 1) -- so it takes (L_1, L_2) = (0, 1) instead (`top`).
+// 8 / 12 coalesced row loads per chunk instead of 28 scattered taps, and ~20
 // registers of staging state instead of 98 -- which is what lets TWO blocks share a CU (175 / 202 -> <= 128 VGPRs): with one,
 // every block's set-up, first-chunk latency and epilogue were exposed (982 -> 790 us and 739 -> 672 us at 256 views).
 // Every staged value is the same expression as Conv3Stager's: fmaf(q3, r3, fmaf(q2, r2, fmaf(q1, r1, q0 * st))), q = (hy hx, hy lx, ly hx, ly lx).
@@ -352,6 +355,7 @@ struct Conv3RowStager {
   int xo0, xo1, xo, dst, Wp;
   float ly[NRT];                           // lower-row weight of tile row r_k, -1 outside the image (wave-uniform at W = 64)
   int Lb[NL], ybase, H;                    // byte offsets of the source rows (kind 2, wave-uniform); image row of r_0
+  bool top;                                // the tile begins at image row 0
   __amdgpu_buffer_rsrc_t rs_a, rs_b;
   int Ca, up_plane4, sk_plane4, wv, so;
 
@@ -379,6 +383,7 @@ struct Conv3RowStager {
     }
     ybase = y0 - 1 + rsub;
     H = A.H;
+    top = y0 == 0;
   }
   // the two border columns of every staged row are zero for the whole kernel (both buffers): written once
   __device__ __forceinline__ void zero_borders(float* tile, int tid, int tstride) const {
@@ -415,7 +420,10 @@ struct Conv3RowStager {
         const int i0 = R == 1 ? (k >> 1) : k, i1 = i0 + 1;      // r_k >> 1
         const float l = fmaxf(ly[k], 0.f), hy = ly[k] < 0.f ? 0.f : 1.f - ly[k];
         const float q0 = hy * hx, q1 = hy * lx, q2 = l * hx, q3 = l * lx;
-        st[k] = fmaf(q3, a[2 * i1 + 1], fmaf(q2, a[2 * i1], fmaf(q1, a[2 * i0 + 1], q0 * a[2 * i0])));
+        float b0 = a[2 * i1], b1 = a[2 * i1 + 1];
+        if (i0 == 0) { b0 = top ? a[4] : b0; b1 = top ? a[5] : b1; }      // image row 0: the second source row is row 1 (L_2)
+        const float v = fmaf(q3, b1, fmaf(q2, b0, fmaf(q1, a[2 * i0 + 1], q0 * a[2 * i0])));
+        st[k] = ly[k] < 0.f ? 0.f : v;      // a row outside the image is zero whatever the clamped source rows hold (0 * NaN)
       } else {
         st[k] = (unsigned)(ybase + R * k) < (unsigned)H ? a[k] : 0.f;
       }
@@ -554,7 +562,7 @@ __global__ __launch_bounds__(512) void conv3x3_lds_kernel(Conv3Args A) {
         float v = fmaf(acc[c][4 * g + e], (&sc.x)[e], (&sh.x)[e]);
         if constexpr (EX) v = conv3_ex_tail(A, n, co, oy, px, v);
         else {
-          if (A.relu) v = fmaxf(v, 0.f);
+          if (A.relu) v = relu_nan(v);
           if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + px];
         }
         A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + px + A.out_off] = v;
@@ -691,8 +699,8 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
-          if (A.relu) v = fmaxf(v, 0.f);
-          v = fmaxf(v, __shfl_xor(v, 1, 64));
+          if (A.relu) v = relu_nan(v);
+          v = max_nan(v, __shfl_xor(v, 1, 64));
           if (!(j & 1) && cbase + e < A.Cout) PH[((cbase + e) * PR + opy[u]) * PW + (opx[u] >> 1)] = v;
         }
     }
@@ -703,7 +711,7 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
       const float* ph = PH + (2 * prow) * PW + pcol;
       const float* wj = HW_ + jn * A.Cout;
       float a = 0.f;
-      for (int c = 0; c < A.Cout; ++c) a = fmaf(fmaxf(ph[c * PR * PW], ph[c * PR * PW + PW]), wj[c], a);
+      for (int c = 0; c < A.Cout; ++c) a = fmaf(max_nan(ph[c * PR * PW], ph[c * PR * PW + PW]), wj[c], a);
       const float v = a + HW_[A.J * A.Cout + jn];
       A.hmap[(((size_t)n * A.J + jn) * h2 + (y0 / 2 + prow)) * w2 + pcol] = 1.0f / (1.0f + expf(-v));
     }
@@ -724,7 +732,7 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
         float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
         if constexpr (EX) v = conv3_ex_tail(A, n, co, oy, opx[u], v);
         else {
-          if (A.relu) v = fmaxf(v, 0.f);
+          if (A.relu) v = relu_nan(v);
           if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + opx[u]];
         }
         A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + opx[u] + A.out_off] = v;
@@ -863,7 +871,7 @@ __global__ __launch_bounds__(512, 4) void conv3x3_s2_kernel(Conv3Args A) {
       for (int u = 0; u < 2; ++u) {
         const int oy = yo0 + opy[u];
         float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
-        if (A.relu) v = fmaxf(v, 0.f);
+        if (A.relu) v = relu_nan(v);
         if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + opx[u]];
         A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + opx[u] + A.out_off] = v;
       }
@@ -1032,7 +1040,7 @@ __global__ __launch_bounds__(64 * (PXB * CG + 1)) void conv3x3_s2p_kernel(Conv3A
 #pragma unroll
         for (int u = 0; u < 2; ++u) {
           float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
-          if (A.relu) v = fmaxf(v, 0.f);
+          if (A.relu) v = relu_nan(v);
           __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v + rv[c][e][u]), ors, ovo[u], (16 * c + e) * A.out_cs * 4, 0);
         }
     }
@@ -1387,7 +1395,7 @@ __global__ __launch_bounds__(256) void pool_head_kernel(const float* __restrict_
   for (int c = 0; c < C; ++c) {
     const float* p = x + (((size_t)n * C + c) * H + 2 * yo) * W + 2 * xo;
     const float2 r0 = *reinterpret_cast<const float2*>(p), r1 = *reinterpret_cast<const float2*>(p + W);
-    const float pooled = fmaxf(fmaxf(r0.x, r0.y), fmaxf(r1.x, r1.y));
+    const float pooled = max_nan(max_nan(r0.x, r0.y), max_nan(r1.x, r1.y));
 #pragma unroll
     for (int jn = 0; jn < 32; ++jn)
       if (jn < J) acc[jn] = fmaf(pooled, ws[jn * C + c], acc[jn]);

@@ -531,3 +531,175 @@ def test_gemm_forms_restatements_against_torch():
         assert torch.allclose(gu.narrow_ref(t, wn, bn, base), ref, rtol=0, atol=1e-10)
         assert float((gu.narrow_ref(t, wn, bn, base, fp32=True).double() - ref).abs().max()) < 2e-3
         assert torch.allclose(gu.narrow_ref(t, wn), F.linear(t.double(), wn.double()), rtol=0, atol=1e-10)
+
+
+# ---- tests/conv_forms_util.py: the route mirror of csrc/decode.hip ------------------------------------------------------------
+def test_conv_forms_route_literals():
+    """conv_forms_util.route on every branch and boundary of decode.hip's launchers, as literal expectations"""
+    import conv_forms_util as cu
+    r = cu.route
+    # 16-row fragments where they pad less, at most five tiles; else 32-row tiles, five at most
+    assert [cu.m16(c) for c in (1, 16, 17, 32, 33, 48, 49, 65, 80, 81, 96, 97, 112)] == \
+        [True, True, False, False, True, True, False, True, True, False, False, False, False]
+    assert r("conv3", 8, 80, 16, 16) == ("lds16", 5, False, 0, False, False) and r("conv3", 8, 96, 16, 16) == ("lds", 3, False, False, False)
+    assert r("conv3", 8, 100, 16, 16) == ("lds", 4, False, False, False) and r("conv3", 8, 160, 16, 16, ex=True) == ("lds", 5, False, False, True)
+    assert r("conv3", 8, 40, 16, 16, ex=True) == ("lds16", 3, False, 0, False, True) and r("conv3", 8, 9, 4, 64) == ("lds16", 1, False, 0, False, False)
+    assert r("conv3", 8, 161, 16, 16) == ("direct", 3, 2, False) and r("conv3", 8, 320, 8, 8) == ("direct", 5, 2, False)
+    # the LDS rule: W divides 256, H whole tiles, 8 (TR + 2)(W + 2) staged floats <= 7 x 512 = 3584 (W = 2 would need 4160)
+    assert [8 * (256 // w + 2) * (w + 2) for w in (2, 4, 8, 16, 32, 64)] == [4160, 3168, 2720, 2592, 2720, 3168]
+    assert not cu.lds_ok(40, 128, 2) and cu.lds_ok(40, 64, 4) and not cu.lds_ok(40, 32, 4) and cu.lds_ok(40, 4, 64) and not cu.lds_ok(40, 6, 64)
+    assert not cu.lds_ok(40, 2, 128) and not cu.lds_ok(40, 16, 48) and cu.lds_ok(160, 16, 16) and not cu.lds_ok(161, 16, 16)
+    # the direct kernel's tiling: channel tiles 5 | 3 | 2 | 1 by divisibility, two pixel tiles where their count is even
+    assert r("conv3", 8, 32, 4, 8) == ("direct", 1, 1, False) and r("conv3", 8, 224, 8, 8) == ("direct", 1, 2, False)
+    assert r("conv3", 8, 96, 2, 48, ex=True) == ("direct", 3, 1, True) and r("conv3", 8, 40, 16, 16, 2) == ("direct", 2, 2, False)
+    assert r("conv3", 8, 160, 8, 16, 2) == ("direct", 5, 1, False) and r("conv3", 8, 480, 8, 8) == ("direct", 5, 2, False)
+    assert r("conv3", 12, 40, 16, 16) is None and r("conv3", 8, 40, 16, 16, 3) is None and r("conv3", 8, 40, 6, 8) is None
+    assert r("conv3", 8, 40, 15, 16, 2) is None and r("conv3", 40, 40, 4096, 4096) is None
+    # the fused input: the row stager by width and switch, the pinned pipeline for five 32-row tiles
+    assert r("upcat", (80, 40), 40, 64, 64) == ("lds16", 3, True, 64, False, False) and r("upcat", (160, 80), 80, 32, 32) == ("lds16", 5, True, 32, False, False)
+    assert r("upcat", (80, 40), 40, 64, 64, row_stager=2) == ("lds16", 3, True, 0, False, False)
+    assert r("upcat", (160, 80), 80, 32, 32, row_stager=1) == ("lds16", 5, True, 0, False, False)
+    assert r("upcat", (16, 8), 16, 16, 16) == ("lds16", 1, True, 0, False, False)
+    assert r("upcat", (320, 160), 160, 16, 16) == ("lds", 5, True, True, False) and r("upcat", (320, 160), 160, 16, 16, pin32=0) == ("lds", 5, True, False, False)
+    assert r("upcat", (0, 16), 128, 32, 8) == ("lds", 4, True, False, False) and r("upcat", (16, 0), 32, 64, 4) == ("lds", 1, True, False, False)
+    for ca, cb, cout, h, w in cu.UPCAT_REFUSED + [(0, 0, 40, 16, 16), (8, 8, 40, 16, 15)]:
+        assert r("upcat", (ca, cb), cout, h, w) is None
+    # the fused read-out head: three 16-row tiles, W = 64, the row stager, and room in the staging tile (6400 floats)
+    assert r("pool_head", (80, 40), 40, 64, 64, j=21) == ("lds16", 3, True, 64, True, False)
+    assert [cu.pool_head_fits(*cj) for cj in ((40, 31), (40, 32), (48, 5), (48, 6), (33, 32))] == [True, False, True, False, True]
+    assert 40 * 128 + 31 * 41 <= 6400 < 40 * 128 + 32 * 41 and 48 * 128 + 5 * 49 <= 6400 < 48 * 128 + 6 * 49
+    for kw in (dict(cout=32), dict(cout=49), dict(cout=64), dict(j=33), dict(j=0), dict(w=32), dict(h=6), dict(row_stager=2), dict(pool_fused=0),
+               dict(cin=(0, 40)), dict(cin=(80, 0)), dict(cin=(12, 40))):
+        args = dict(cin=(80, 40), cout=40, h=64, w=64, j=21)
+        args.update(kw)
+        assert r("pool_head", **args) is None, kw
+    # the stride-2 family: three shapes, two kernels; persistent blocks per CU by the tile count
+    assert r("down2", 40, 80, 64, 64) == ("s2p", 4, 1, 18, 4) and r("down2", 80, 160, 32, 32) == ("s2p", 2, 2, 9, 4)
+    assert r("down2", 8, 320, 16, 16) == ("s2p", 1, 4, 5, 4) and r("down2", 8, 320, 16, 16, s2_staging_wave=0) == ("s2", 2, 4, 5)
+    assert r("down2", 40, 80, 64, 64, s2_staging_wave=0) == ("s2", 8, 1, 18) and r("down2", 24, 160, 32, 32, s2_staging_wave=0) == ("s2", 4, 2, 10)
+    for cin, cout, h, w in cu.DOWN2_REFUSED + [(40, 80, 32, 32), (40, 160, 64, 64)]:
+        assert r("down2", cin, cout, h, w) is None
+    assert [cu.s2_blocks_per_cu(t, 256) for t in (1, 256, 257, 768, 769, 1024, 1025, 1792, 1793, 2048)] == [3, 3, 3, 3, 2, 2, 3, 2, 3, 3]
+    assert cu.s2_blocks_per_cu(1024, 256, 4) == 4 and cu.s2p_grid(960, 16, 256) == (1920, 768) and cu.s2p_grid(3, 64, 256) == (24, 24)
+    # feat_in + bilinear x2: 8 x 8 maps, whole 32-channel tiles, (K + C) x 64 floats within 160 KiB
+    assert r("up2", 320, 160, 8, 8) == ("conv1x1_up2", 10) and r("up2", 448, 192, 8, 8) == ("conv1x1_up2", 10)
+    assert r("up2", 456, 192, 8, 8) is None and r("up2", 40, 48, 8, 8) is None and r("up2", 12, 32, 8, 8) is None and r("up2", 40, 32, 16, 16) is None
+    assert r("pool", 64, 0, 2, 2, j=32) == ("pool_head",) and r("pool", 65, 0, 2, 2, j=1) is None and r("pool", 8, 0, 2, 3, j=1) is None
+    # the case tables name what they claim
+    assert {r("conv3", *c)[1:3] for c in cu.DIRECT_CASES} == {(ct, pt) for ct in (1, 2, 3, 5) for pt in (1, 2)}
+    assert all(r("conv3", *c)[0] == "direct" for c in cu.DIRECT_CASES)
+    lds = cu.lds_cases()
+    assert len(lds) == 75 and all(r("conv3", *c)[0] == ("lds16" if cu.m16(c[1]) else "lds") for c in lds)
+    for fam, couts in (("lds", cu.LDS_COUTS), ("lds16", cu.LDS16_COUTS)):
+        mine = [c for c in lds if c[1] in couts]
+        assert {(c[3], c[2] * c[3] // 256) for c in mine} == {(w, m) for w in cu.LDS_WIDTHS for m in (1, 2, 3)}, fam
+        assert {(c[3], c[0]) for c in mine} == {(w, k) for w in cu.LDS_WIDTHS for k in cu.CINS}, fam
+    assert {r("conv3", *c)[1] for c in lds if not cu.m16(c[1])} == {1, 2, 3, 4, 5} and {r("conv3", *c)[1] for c in lds if cu.m16(c[1])} == {1, 3, 5}
+    up = cu.upcat_cases()
+    assert len(up) == 100 and all(r("upcat", (ca, cb), cout, h, w) is not None for ca, cb, cout, h, w in up)
+    for cout in cu.UPCAT_COUTS:
+        assert {(c[0], c[1]) for c in up if c[2] == cout} == set(cu.CACB) and {(c[3], c[4]) for c in up if c[2] == cout} == set(cu.UPCAT_SHAPES)
+    forms = {r("upcat", (ca, cb), cout, h, w, **kw) for ca, cb, cout, h, w in up
+             for kw in ({}, dict(row_stager=0), dict(row_stager=1), dict(row_stager=2), dict(pin32=0))}
+    assert forms == {("lds", ct, True, False, False) for ct in (1, 2, 3, 4, 5)} | {("lds", 5, True, True, False)} | \
+        {("lds16", ct, True, rw, False, False) for ct in (1, 3, 5) for rw in (0, 64, 32)}
+    for ca, cb, cout, j, h, taken in cu.POOL_HEAD_CASES:
+        assert (r("pool_head", (ca, cb), cout, h, 64, j=j) is not None) == taken
+    for k, c, taken in cu.UP2_CASES:
+        assert (r("up2", k, c, 8, 8) is not None) == taken
+
+
+def test_conv_forms_restatements_and_poison():
+    """the restatements against torch, and what a poisoned pixel reaches on the CPU: exactly its 3 x 3 neighbourhood"""
+    import conv_forms_util as cu
+    F = torch.nn.functional
+    g = torch.Generator().manual_seed(1)
+    x, wt, scale, shift, res = cu.conv_data(g, 2, 8, 5, 6, 8, False)
+    y = F.conv2d(x.double(), wt.double(), padding=1) * scale.double().view(1, -1, 1, 1) + shift.double().view(1, -1, 1, 1)
+    assert torch.equal(cu.conv3_ref(x, wt, scale, shift, torch.float64, res=res), torch.relu(y) + res.double())
+    assert torch.equal(cu.conv3_ref(x, wt, scale, shift, torch.float64, res=res, res_pre=1), torch.relu(y + res.double()))
+    assert torch.equal(cu.conv3_ref(x, wt, scale, shift, torch.float64, relu=0), y)
+    xi, wi, si, hi, ri = cu.conv_data(g, 2, 8, 5, 6, 8, True)
+    assert torch.equal(cu.conv3_ref(xi, wi, si, hi, torch.float32, 2, res=ri[:, :, :3, :4]).double(),
+                       cu.conv3_ref(xi, wi, si, hi, torch.float64, 2, res=ri[:, :, :3, :4]))
+    a, b = cu.upcat_data(g, 2, 8, 8, 6, 8, True)
+    up = cu.upcat_ref(a, b, torch.float32)
+    assert tuple(up.shape) == (2, 16, 6, 8) and torch.equal(up, up.round()) and torch.equal(up[:, 8:], b)
+    assert tuple(cu.upcat_ref(a, None, torch.float64).shape) == (2, 8, 6, 8) and torch.equal(cu.upcat_ref(a[:, :0], b, torch.float32), b)
+    for variant in cu.POISONS:
+        bad = cu.poison(x, variant)
+        assert int((~torch.isfinite(bad)).sum()) == 1 and bool(torch.isfinite(bad[0]).all())
+        clean, out = cu.conv3_ref(x, wt, scale, shift, torch.float32, relu=0), cu.conv3_ref(bad, wt, scale, shift, torch.float32, relu=0)
+        hit = F.max_pool2d((~torch.isfinite(bad)).any(dim=1, keepdim=True).float(), 3, 1, 1).bool().expand_as(out)
+        assert torch.equal(~torch.isfinite(out), hit) and torch.equal(out[~hit], clean[~hit])
+    hw, hb = torch.randn(3, 5, generator=g), torch.randn(3, generator=g)
+    yn = cu.poison(y.float(), "nan00")
+    head = cu.head_ref(yn, hw, hb, torch.float32)
+    assert bool(head[1, :, 0, 0].isnan().all()) and int(head.isnan().sum()) == 3
+    assert torch.allclose(cu.head_ref(y, hw, hb, torch.float64),
+                          torch.sigmoid(F.conv2d(F.max_pool2d(y, 2, 2), hw.double()[:, :, None, None], hb.double())), rtol=0, atol=1e-12)
+    xk, wk, bk = torch.randn(2, 8, 8, 8, generator=g), torch.randn(32, 8, generator=g), torch.randn(32, generator=g)
+    low = F.interpolate(torch.einsum("oc,nchw->nohw", wk.double(), xk.double()) + bk.double().view(1, -1, 1, 1), scale_factor=2, mode="bilinear")
+    assert torch.allclose(cu.up2_ref(xk, wk, bk, torch.float64), low, rtol=0, atol=1e-12)      # the 1x1 convolution commutes with it
+
+
+def _decode_stage_forms():
+    """(what, form) of every launch the decoders make, by the tables of poem_v2_amd.decode (no device needed)"""
+    import conv_forms_util as cu
+    from poem_v2_amd import decode as dc
+    out = []
+    f = dc.FEAT_SIZES["HRNet"]
+    for i, side in enumerate((64, 32, 16)):
+        out.append((f"HRNet feat_delayer.{i}", cu.route("down2", f[i], f[i + 1], side, side)))
+        out.append((f"HRNet feat_delayer.{i} direct", cu.route("conv3", f[i], f[i + 1], side, side, 2)))
+    out.append(("HRNet feat_in", cu.route("up2", f[3], f[2], 8, 8)))
+    for i, side in enumerate((16, 32, 64)):
+        out.append((f"HRNet uv_delayer.{i}", cu.route("upcat", (f[3 - i], f[2 - i]), f[2 - i], side, side)))
+        out.append((f"HRNet uv_delayer.{i} two launches", cu.route("conv3", f[3 - i] + f[2 - i], f[2 - i], side, side)))
+    out.append(("HRNet uv_delayer.2 + uv_out", cu.route("pool_head", (f[1], f[0]), f[0], 64, 64, j=dc.NUM_JOINTS)))
+    out.append(("HRNet uv_out", cu.route("pool", f[0], 0, 64, 64, j=dc.NUM_JOINTS)))
+    for name in ("resnet18", "resnet34", "resnet50"):
+        f = dc.FEAT_SIZES[name]
+        for h0, w0 in ((8, 8), (4, 8)):
+            for i in range(3):
+                ca, cb, cout, h, w = f[3 - i], f[2 - i], f[2 - i], h0 << (i + 1), w0 << (i + 1)
+                if ca + cb > dc.K_SPLIT:           # _SplitConv3x3: groups of at most K_SPLIT channels, the last one through poem_conv3x3_ex
+                    spans = [min(c0 + dc.K_SPLIT, ca) - c0 for c0 in range(0, ca, dc.K_SPLIT)] + \
+                        [min(c0 + dc.K_SPLIT, cb) - c0 for c0 in range(0, cb, dc.K_SPLIT)]
+                    for k, cin in enumerate(spans):
+                        out.append((f"{name} stage {i} group {k}", cu.route("conv3", cin, cout, h, w, ex=k + 1 == len(spans))))
+                    continue
+                form = cu.route("upcat", (ca, cb), cout, h, w)
+                out.append((f"{name} stage {i} {h}x{w}", form if form is not None else cu.route("conv3", ca + cb, cout, h, w)))
+                out.append((f"{name} stage {i} {h}x{w} two launches", cu.route("conv3", ca + cb, cout, h, w)))
+            if f[0] <= 64:
+                out.append((f"{name} uv_out", cu.route("pool", f[0], 0, h0 << 3, w0 << 3, j=dc.NUM_JOINTS)))
+    return out
+
+
+def test_every_caller_shape_lands_on_a_tested_conv_form():
+    """every conv3 / down2 launch of the HRNet-W40 and ResNet-18/34/50 plans and every stage of both decoder branches maps
+    through the route mirror to a form tests/test_conv_forms.py has a case for: a new caller shape on an untested form fails here"""
+    import conv_forms_util as cu
+    from poem_v2_amd import backbone as bb
+    from poem_v2_amd import resnet as rn
+    tested = cu.tested_forms()
+    assert len(tested) == 8 * 2 + 5 * 2 + 3 * 2 + 6 + 9 + 1 + 6 + 2, sorted(tested)
+    seen = set()
+    plans = [("hrnet", bb.HipPlan(2, h, w)) for h, w in ((256, 256), (128, 256))]
+    plans += [(f"resnet{v}", rn.ResNetPlan(2, h, w, v)) for v in (18, 34, 50) for h, w in ((256, 256), (128, 256))]
+    for name, plan in plans:
+        for op in plan.ops:
+            if op["kind"] == "conv3":
+                form = cu.route("conv3", op["in"].c, op["out"].c, op["in"].h, op["in"].w, op["stride"], ex=True)
+            elif op["kind"] == "down2":
+                form = cu.route("down2", op["in"].c, op["out"].c, op["in"].h, op["in"].w)
+            else:
+                continue
+            assert form is not None and form in tested, (name, op["conv"], form)
+            seen.add(form)
+    for what, form in _decode_stage_forms():
+        assert form is not None and form in tested, (what, form)
+        seen.add(form)
+    print(f"{len(seen)} of {len(tested)} tested forms are in use by a caller")
+    assert ("lds16", 3, True, 64, True, False) in seen and ("s2p", 1, 4, 5, 4) in seen and ("conv1x1_up2", 10) in seen
