@@ -19,7 +19,7 @@
 //       and whose (chunk, tap, k-step) part is a scalar offset of the buffer descriptor.
 //   D layout: lane = pixel, registers = output channels -> the epilogue's stores are 128-byte row segments.
 // A wave owns CT channel tiles x PT pixel tiles; waves are independent (no LDS, no barriers).
-#include "common.h"
+#include "conv.h"
 #include <algorithm>
 #include <type_traits>
 
@@ -84,10 +84,9 @@ struct Conv3Args {
   const float* scale;   // (cot*32) per-channel multiplier   (BatchNorm folded; 1 without norm)
   const float* shift;   // (cot*32) per-channel offset       (conv bias + BatchNorm folded)
   const float* res;     // optional lateral input (views, Cout, Ho, Wo), added after the activation
-  float* out;           // element (n, co, y, x) at out[n * out_ns + co * out_cs + y * out_rs + x + out_off]
+  float* out;           // element (n, co, y, x) at out[omap.at(n, co, y, x)]
   int Cin, Cout, H, W, stride, relu;
-  long out_ns;
-  int out_cs, out_rs, out_off;
+  ConvMap omap;
   int views;
   // fused input (conv3x3_lds_kernel<CT, true>): in = [bilinear x2 of up_a (views, Ca, H/2, W/2) | skip_b (views, Cb, H, W)]
   // with the zero border applied while the halo is staged -- the concatenated tensor never exists
@@ -100,16 +99,16 @@ struct Conv3Args {
   const float* head_b;
   float* hmap;
   int J;
-  // poem_conv3x3_ex (the EX instantiations): the residual addressed as `out` is -- it may be the interior of a zero-bordered
-  // buffer -- and, with res_pre, added BEFORE the activation (a BasicBlock: relu(conv * scale + shift + x))
+  // poem_conv3x3_ex (the EX instantiations): the residual by a map of its own -- it may be the interior of a zero-bordered
+  // buffer -- and, with res_pre, added BEFORE the activation (a BasicBlock: relu(conv * scale + shift + x)).  Every other
+  // instantiation reads the residual as the plain map (Cout, Ho, Wo) and never looks at these two.
   int res_pre;
-  long res_ns;
-  int res_cs, res_rs, res_off;
+  ConvMap rmap;
 };
 
-// epilogue tail of the EX instantiations: activation and residual in either order, the residual by its own strides
+// epilogue tail of the EX instantiations: activation and residual in either order, the residual by its own map
 __device__ __forceinline__ float conv3_ex_tail(const Conv3Args& A, int n, int co, int oy, int ox, float v) {
-  const float r = A.res ? A.res[(size_t)n * A.res_ns + (size_t)co * A.res_cs + oy * A.res_rs + ox + A.res_off] : 0.f;
+  const float r = A.res ? A.res[A.rmap.at(n, co, oy, ox)] : 0.f;
   if (A.res_pre) {
     if (A.res) v += r;
     if (A.relu) v = relu_nan(v);
@@ -119,18 +118,22 @@ __device__ __forceinline__ float conv3_ex_tail(const Conv3Args& A, int n, int co
   }
   return v;
 }
+// ... and of the others: ReLU, then the lateral add from `plain`, the kernel's ConvMap(Cout, Ho, Wo)
+template <bool EX>
+__device__ __forceinline__ float conv3_tail(const Conv3Args& A, const ConvMap& plain, int n, int co, int oy, int ox, float v) {
+  if constexpr (EX) return conv3_ex_tail(A, n, co, oy, ox, v);
+  if (A.relu) v = relu_nan(v);
+  if (A.res) v += A.res[plain.at(n, co, oy, ox)];
+  return v;
+}
 
 template <int CT, int PT, bool EX = false>
 __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args A) {
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, j = lane & 31, h = lane >> 5;
+  const int lane = threadIdx.x & 63, j = lane & 31, h = lane >> 5;
   const int Ho = A.H / A.stride, Wo = A.W / A.stride, Hp = A.H + 2, Wp = A.W + 2;
-  const int ptiles = Ho * Wo / 32, pgroups = ptiles / PT;
-  const int cogroups = ((A.Cout + 31) / 32) / CT;
-  const long item = (long)blockIdx.x * 4 + wv;
-  if (item >= (long)A.views * cogroups * pgroups) return;
-  const int pg = (int)(item % pgroups);
-  const int cg = (int)((item / pgroups) % cogroups);
-  const int n = (int)(item / ((long)pgroups * cogroups));
+  ConvItem it;
+  if (!conv_item(A.views, ((A.Cout + 31) / 32) / CT, Ho * Wo / 32 / PT, it)) return;
+  const int n = it.n, cg = it.cg;
   const int plane = Hp * Wp, KC = A.Cin / 8;
   const __amdgpu_buffer_rsrc_t xrs = frag_rsrc(A.in + (size_t)n * A.Cin * plane, (unsigned)((size_t)A.Cin * plane * 4));
   const __amdgpu_buffer_rsrc_t wrs = frag_rsrc(A.wp, 0xffffffffu);
@@ -139,7 +142,7 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args A) {
   int py[PT], px[PT];
 #pragma unroll
   for (int p = 0; p < PT; ++p) {
-    const int pix = (pg * PT + p) * 32 + j;
+    const int pix = (it.pg * PT + p) * 32 + j;
     py[p] = pix / Wo;
     px[p] = pix % Wo;
     xoff[p] = (4 * h * plane + py[p] * A.stride * Wp + px[p] * A.stride) * 4;
@@ -149,67 +152,17 @@ __global__ __launch_bounds__(256) void conv3x3_kernel(Conv3Args A) {
   for (int c = 0; c < CT; ++c)
 #pragma unroll
     for (int p = 0; p < PT; ++p) acc[c][p] = zero16();
-  const int wbase = (cg * CT) * 9 * KC * 1024;        // bytes
-  // Two-stage software pipeline over the 9 * KC (tap, 8-channel chunk) steps with pinned order (sched_barrier): the
-  // operands of step q+1 are in flight while the 4*CT*PT MFMAs of step q issue.
-  const int total = 9 * KC;
-  int tap = 0, cc = 0, q = 0;
-  float4 a0[CT], a1[CT];
-  float b0[PT][4], b1[PT][4];
-#define POEM_CLOAD(A, B)                                                                                          \
-  {                                                                                                               \
-    const int woff_ = wbase + (tap * KC + cc) * 1024;                                                             \
-    const int soff_ = cc * 8 * plane * 4 + ((tap / 3) * Wp + (tap % 3)) * 4;                                      \
-    _Pragma("unroll") for (int c = 0; c < CT; ++c) A[c] = frag_load(wrs, lane * 16, woff_ + c * 9 * KC * 1024);   \
-    _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                                 \
-      _Pragma("unroll") for (int p = 0; p < PT; ++p)                                                              \
-        B[p][t] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(xrs, xoff[p], soff_ + t * plane * 4, 0)); \
-    if (q + 1 < total) { ++q; if (++cc == KC) { cc = 0; ++tap; } }   /* saturates on the last step */              \
-  }
-#define POEM_CMMA(A, B)                                                                                           \
-  _Pragma("unroll") for (int t = 0; t < 4; ++t)                                                                   \
-    _Pragma("unroll") for (int c = 0; c < CT; ++c)                                                                \
-      _Pragma("unroll") for (int p = 0; p < PT; ++p) acc[c][p] = mfma32((&A[c].x)[t], B[p][t], acc[c][p]);
-  POEM_CLOAD(a0, b0)
-  int done = 0;
-  for (; done + 1 < total; done += 2) {
-    POEM_CLOAD(a1, b1)
-    __builtin_amdgcn_sched_barrier(0);
-    POEM_CMMA(a0, b0)
-    __builtin_amdgcn_sched_barrier(0);
-    POEM_CLOAD(a0, b0)
-    __builtin_amdgcn_sched_barrier(0);
-    POEM_CMMA(a1, b1)
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  if (done < total) { POEM_CMMA(a0, b0) }   // odd step count: the last step is already in (a0, b0)
-#undef POEM_CLOAD
-#undef POEM_CMMA
-  // epilogue: affine (conv bias + BatchNorm), ReLU, lateral add; lane = pixel, register e = channel 8(e>>2) + 4h + (e&3)
+  conv_direct_loop<CT, PT, 9>(acc, xrs, wrs, xoff, lane, (cg * CT) * 9 * KC * 1024, KC, plane, Wp);
+  // epilogue: affine (conv bias + BatchNorm), ReLU, lateral add
+  const ConvMap plain(A.Cout, Ho, Wo);
+  tile32_channels<CT>(cg * CT, h, A.Cout, [&](int cb) { return affine4(A.scale, A.shift, cb); },
+                      [&](int co, int c, int r, const Affine4& f) {
 #pragma unroll
-  for (int c = 0; c < CT; ++c) {
-    const int cbase = (cg * CT + c) * 32 + 4 * h;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 sc = *reinterpret_cast<const float4*>(A.scale + cbase + 8 * g);
-      const float4 sh = *reinterpret_cast<const float4*>(A.shift + cbase + 8 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int co = cbase + 8 * g + e;
-        if (co >= A.Cout) continue;
-#pragma unroll
-        for (int p = 0; p < PT; ++p) {
-          float v = fmaf(acc[c][p][4 * g + e], (&sc.x)[e], (&sh.x)[e]);
-          if constexpr (EX) v = conv3_ex_tail(A, n, co, py[p], px[p], v);
-          else {
-            if (A.relu) v = relu_nan(v);
-            if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + py[p] * Wo + px[p]];
-          }
-          A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + py[p] * A.out_rs + px[p] + A.out_off] = v;
-        }
-      }
+    for (int p = 0; p < PT; ++p) {
+      const float v = fmaf(acc[c][p][r], (&f.sc.x)[r & 3], (&f.sh.x)[r & 3]);
+      A.out[A.omap.at(n, co, py[p], px[p])] = conv3_tail<EX>(A, plain, n, co, py[p], px[p], v);
     }
-  }
+  });
 }
 
 // Staging of one 8-channel chunk of a convolution's input tile -- (TR + 2) x (W + 2) per channel, zero border included --
@@ -253,37 +206,11 @@ struct Conv3Stager {
       }
       const int y = y0 + o / Wp - 1, x = o % Wp - 1;
       const bool valid = y >= 0 && y < A.H && x >= 0 && x < W;
-      const float sy = fmaxf((y + 0.5f) * 0.5f - 0.5f, 0.f), sx = fmaxf((x + 0.5f) * 0.5f - 0.5f, 0.f);
-      const int yy0 = (int)sy, xx0 = (int)sx;
-      const int yy1 = min(yy0 + 1, h2 - 1), xx1 = min(xx0 + 1, w2 - 1);
-      const float ly = sy - (float)yy0, lx = sx - (float)xx0, hy = 1.f - ly, hx = 1.f - lx;
-      q0[u] = valid ? hy * hx : 0.f; q1[u] = valid ? hy * lx : 0.f; q2[u] = valid ? ly * hx : 0.f; q3[u] = valid ? ly * lx : 0.f;
+      const Up2Tap ty = up2_tap(y, h2), tx = up2_tap(x, w2);
+      q0[u] = valid ? ty.h * tx.h : 0.f; q1[u] = valid ? ty.h * tx.l : 0.f; q2[u] = valid ? ty.l * tx.h : 0.f; q3[u] = valid ? ty.l * tx.l : 0.f;
       const int base = valid ? chl * up_plane4 : 0;
-      o0[u] = valid ? base + (yy0 * w2 + xx0) * 4 : 0; o1[u] = valid ? base + (yy0 * w2 + xx1) * 4 : 0;
-      o2[u] = valid ? base + (yy1 * w2 + xx0) * 4 : 0; o3[u] = valid ? base + (yy1 * w2 + xx1) * 4 : 0;
-      ob[u] = valid ? chl * sk_plane4 + (y * W + x) * 4 : -1;
-    }
-  }
-  // Stride-2 convolution (padding 1) of an UNBORDERED input (views, C, H, W) = A.skip_b: output rows [yo0, yo0 + 8) need input
-  // rows 2 yo0 - 1 .. 2 yo0 + 15 (17) and columns -1 .. W - 1; staged per channel as [row][column parity][column / 2] (row
-  // stride 2 RS, RS = W / 2 + 1) so that the 16 consecutive output columns of a unit read consecutive LDS words whatever the
-  // tap (input column 2 xo + tx - 1 -> parity tx & 1, half index xo + (tx >> 1)).  Every chunk is of kind 1; positions
-  // outside the image get offset -1 -> zero.
-  __device__ __forceinline__ void init_s2(const Conv3Args& A, int n, int yo0, int tid, int tstride, int nthreads) {
-    const int W = A.W, RS = W / 2 + 1, tplane = 17 * 2 * RS;
-    count = 8 * tplane;
-    Ca = 0;
-    up_plane4 = 0; in_plane4 = 0; sk_plane4 = A.H * W * 4;
-    rs_b = frag_rsrc(A.skip_b + (size_t)n * A.Cin * (A.H * W), (unsigned)((size_t)A.Cin * sk_plane4));
-    rs_a = rs_b;
-#pragma unroll
-    for (int u = 0; u < MAXLD; ++u) {
-      const int i = min(tid + nthreads * u, count - 1);
-      const int chl = i / tplane, o = i % tplane;
-      const int r = o / (2 * RS), pp = (o / RS) & 1, xh = o % RS;
-      const int y = 2 * yo0 - 1 + r, x = 2 * xh + pp - 1;
-      const bool valid = y >= 0 && y < A.H && x >= 0 && x < W;
-      sdst[u] = chl * tstride + o;
+      o0[u] = valid ? base + (ty.i0 * w2 + tx.i0) * 4 : 0; o1[u] = valid ? base + (ty.i0 * w2 + tx.i1) * 4 : 0;
+      o2[u] = valid ? base + (ty.i1 * w2 + tx.i0) * 4 : 0; o3[u] = valid ? base + (ty.i1 * w2 + tx.i1) * 4 : 0;
       ob[u] = valid ? chl * sk_plane4 + (y * W + x) * 4 : -1;
     }
   }
@@ -367,10 +294,9 @@ struct Conv3RowStager {
     up_plane4 = h2 * w2 * 4; sk_plane4 = A.H * W * 4;
     rs_a = frag_rsrc(A.up_a + (size_t)n * A.Ca * (h2 * w2), (unsigned)((size_t)A.Ca * up_plane4));
     rs_b = frag_rsrc(A.skip_b + (size_t)n * A.Cb * (A.H * W), (unsigned)((size_t)A.Cb * sk_plane4));
-    const float sx = fmaxf((x + 0.5f) * 0.5f - 0.5f, 0.f);
-    const int xx0 = (int)sx, xx1 = min(xx0 + 1, w2 - 1);
-    lx = sx - (float)xx0; hx = 1.f - lx;
-    xo0 = xx0 * 4; xo1 = xx1 * 4; xo = x * 4;
+    const Up2Tap tx = up2_tap(x, w2);
+    lx = tx.l; hx = tx.h;
+    xo0 = tx.i0 * 4; xo1 = tx.i1 * 4; xo = x * 4;
     dst = wv * tstride + rsub * Wp + x + 1;
 #pragma unroll
     for (int i = 0; i < NL; ++i) Lb[i] = min(max(y0 / 2 - 1 + i, 0), h2 - 1) * w2 * 4;
@@ -378,8 +304,7 @@ struct Conv3RowStager {
     for (int k = 0; k < NRT; ++k) {
       const int y = y0 - 1 + rsub + R * k;
       const bool valid = y >= 0 && y < A.H;
-      const float sy = fmaxf((y + 0.5f) * 0.5f - 0.5f, 0.f);
-      ly[k] = valid ? sy - (float)(int)sy : -1.f;
+      ly[k] = valid ? up2_tap(y, h2).l : -1.f;
     }
     ybase = y0 - 1 + rsub;
     H = A.H;
@@ -546,29 +471,14 @@ __global__ __launch_bounds__(512) void conv3x3_lds_kernel(Conv3Args A) {
 #undef POEM_T32_LOADB
 #undef POEM_T32_MMA
 #undef POEM_T32_STEP
-  // epilogue: affine (conv bias + BatchNorm), ReLU, lateral add; lane = pixel, register e = channel 8(e>>2) + 4h + (e&3)
-  const int Ho = A.H, Wo = A.W, oy = y0 + py;
-#pragma unroll
-  for (int c = 0; c < CT; ++c) {
-    const int cbase = c * 32 + 4 * h;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-      const float4 sc = *reinterpret_cast<const float4*>(A.scale + cbase + 8 * g);
-      const float4 sh = *reinterpret_cast<const float4*>(A.shift + cbase + 8 * g);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const int co = cbase + 8 * g + e;
-        if (co >= A.Cout) continue;
-        float v = fmaf(acc[c][4 * g + e], (&sc.x)[e], (&sh.x)[e]);
-        if constexpr (EX) v = conv3_ex_tail(A, n, co, oy, px, v);
-        else {
-          if (A.relu) v = relu_nan(v);
-          if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + px];
-        }
-        A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + px + A.out_off] = v;
-      }
-    }
-  }
+  // epilogue: affine (conv bias + BatchNorm), ReLU, lateral add
+  const int oy = y0 + py;
+  const ConvMap plain(A.Cout, A.H, A.W);
+  tile32_channels<CT>(0, h, A.Cout, [&](int cb) { return affine4(A.scale, A.shift, cb); },
+                      [&](int co, int c, int r, const Affine4& f) {
+    const float v = fmaf(acc[c][r], (&f.sc.x)[r & 3], (&f.sh.x)[r & 3]);
+    A.out[A.omap.at(n, co, oy, px)] = conv3_tail<EX>(A, plain, n, co, oy, px, v);
+  });
 }
 
 // The LDS-staged kernel above on v_mfma_f32_16x16x4_f32, for output widths that are not multiples of 32: Cout = 40 (the last
@@ -689,21 +599,17 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
     float* HW_ = tile + A.Cout * PR * PW;             // J x Cout weights | J biases  (launcher: fits the staging tile)
     for (int i = tid; i < A.J * A.Cout; i += 512) HW_[i] = A.head_w[i];
     for (int i = tid; i < A.J; i += 512) HW_[A.J * A.Cout + i] = A.head_b[i];
+    // (a skipped channel is skipped by both lanes of an exchange: they share g)
+    tile16_channels<CT16>(0, g, A.Cout, [&](int cb) { return affine4(A.scale, A.shift, cb); },
+                          [&](int co, int c, int e, const Affine4& f) {
 #pragma unroll
-    for (int c = 0; c < CT16; ++c) {
-      const int cbase = c * 16 + 4 * g;
-      const float4 sc = *reinterpret_cast<const float4*>(A.scale + cbase);
-      const float4 sh = *reinterpret_cast<const float4*>(A.shift + cbase);
-#pragma unroll
-      for (int e = 0; e < 4; ++e)
-#pragma unroll
-        for (int u = 0; u < 2; ++u) {
-          float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
-          if (A.relu) v = relu_nan(v);
-          v = max_nan(v, __shfl_xor(v, 1, 64));
-          if (!(j & 1) && cbase + e < A.Cout) PH[((cbase + e) * PR + opy[u]) * PW + (opx[u] >> 1)] = v;
-        }
-    }
+      for (int u = 0; u < 2; ++u) {
+        float v = fmaf(acc[c][u][e], (&f.sc.x)[e], (&f.sh.x)[e]);
+        if (A.relu) v = relu_nan(v);
+        v = max_nan(v, __shfl_xor(v, 1, 64));
+        if (!(j & 1)) PH[(co * PR + opy[u]) * PW + (opx[u] >> 1)] = v;
+      }
+    });
     __syncthreads();
     const int h2 = Ho / 2, w2 = Wo / 2;
     for (int o = tid; o < A.J * 2 * PW; o += 512) {
@@ -717,35 +623,23 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
     }
     return;
   }
+  const ConvMap plain(A.Cout, Ho, Wo);
+  tile16_channels<CT16>(0, g, A.Cout, [&](int cb) { return affine4(A.scale, A.shift, cb); },
+                        [&](int co, int c, int e, const Affine4& f) {
 #pragma unroll
-  for (int c = 0; c < CT16; ++c) {
-    const int cbase = c * 16 + 4 * g;
-    const float4 sc = *reinterpret_cast<const float4*>(A.scale + cbase);
-    const float4 sh = *reinterpret_cast<const float4*>(A.shift + cbase);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int co = cbase + e;
-      if (co >= A.Cout) continue;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int oy = y0 + opy[u];
-        float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
-        if constexpr (EX) v = conv3_ex_tail(A, n, co, oy, opx[u], v);
-        else {
-          if (A.relu) v = relu_nan(v);
-          if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + opx[u]];
-        }
-        A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + opx[u] + A.out_off] = v;
-      }
+    for (int u = 0; u < 2; ++u) {
+      const int oy = y0 + opy[u];
+      const float v = fmaf(acc[c][u][e], (&f.sc.x)[e], (&f.sh.x)[e]);
+      A.out[A.omap.at(n, co, oy, opx[u])] = conv3_tail<EX>(A, plain, n, co, oy, opx[u], v);
     }
-  }
+  });
 }
 
 // The three stride-2 ConvBlocks of feat_decode (POEM.py:183-189: 40 -> 80 at 64^2, 80 -> 160 at 32^2, 160 -> 320 at 16^2; each
 // 59 MFLOP per view) on the LDS staging, 16x16x4 tiles.  Round 2 ran them on the direct kernel (every tap of every wave a
 // strided global gather: 40 TFLOP/s) over zero-bordered copies.  Here a block of 8 waves owns 8 output rows of a view =
 // PXB pixel tiles of 32, and CG groups of five 16-channel tiles (wave = one pixel tile x one group): (PXB, CG) = (8, 1),
-// (4, 2), (2, 4) for the three layers -- the input is read unbordered (Conv3Stager::init_s2), the output written plain.
+// (4, 2), (2, 4) for the three layers -- the input is read unbordered (the LDS-DMA offsets below), the output written plain.
 template <int PXB, int CG, int MAXLD>
 __global__ __launch_bounds__(512, 4) void conv3x3_s2_kernel(Conv3Args A) {
   constexpr int CT16 = 5;
@@ -753,7 +647,7 @@ __global__ __launch_bounds__(512, 4) void conv3x3_s2_kernel(Conv3Args A) {
   extern __shared__ __attribute__((aligned(16))) float tile[];      // 2 x 8 x tstride
   const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, j = lane & 15, g = lane >> 4;
   const int W = A.W, Wo = W / 2, Ho = A.H / 2, RS = W / 2 + 1, KC = A.Cin / 8;
-  // staged plane of a channel: 17 rows x 2 column parities x RS (see Conv3Stager::init_s2), padded to whole waves of 64 floats
+  // staged plane of a channel: 17 rows x 2 column parities x RS (see `voff` below), padded to whole waves of 64 floats
   // so that one wave-wide LDS-DMA request (lane l -> LDS base + 4 l) never straddles two channels; + 16: bank offset of planes
   const int tplane = 17 * 2 * RS, tpad = (tplane + 63) & ~63, tstride = tpad + 16;
   const int rblocks = Ho / 8;
@@ -858,25 +752,16 @@ __global__ __launch_bounds__(512, 4) void conv3x3_s2_kernel(Conv3Args A) {
 #undef POEM_S2_MMA
 #undef POEM_S2_STEP
   // epilogue: lane (g, j) holds channels 80 cgrp + 16c + 4g + e of output pixel (unit u, j)
+  const ConvMap plain(A.Cout, Ho, Wo);
+  tile16_channels<CT16>(cgrp * (CT16 * 16), g, A.Cout, [&](int cb) { return affine4(A.scale, A.shift, cb); },
+                        [&](int co, int c, int e, const Affine4& f) {
 #pragma unroll
-  for (int c = 0; c < CT16; ++c) {
-    const int cbase = cgrp * (CT16 * 16) + c * 16 + 4 * g;
-    const float4 sc = *reinterpret_cast<const float4*>(A.scale + cbase);
-    const float4 sh = *reinterpret_cast<const float4*>(A.shift + cbase);
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const int co = cbase + e;
-      if (co >= A.Cout) continue;
-#pragma unroll
-      for (int u = 0; u < 2; ++u) {
-        const int oy = yo0 + opy[u];
-        float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
-        if (A.relu) v = relu_nan(v);
-        if (A.res) v += A.res[((size_t)n * A.Cout + co) * (Ho * Wo) + oy * Wo + opx[u]];
-        A.out[(size_t)n * A.out_ns + (size_t)co * A.out_cs + oy * A.out_rs + opx[u] + A.out_off] = v;
-      }
+    for (int u = 0; u < 2; ++u) {
+      const int oy = yo0 + opy[u];
+      const float v = fmaf(acc[c][u][e], (&f.sc.x)[e], (&f.sh.x)[e]);
+      A.out[A.omap.at(n, co, oy, opx[u])] = conv3_tail<false>(A, plain, n, co, oy, opx[u], v);
     }
-  }
+  });
 }
 
 // The stride-2 ConvBlocks with the staging on a wave of its own (round 4).  What held conv3x3_s2_kernel at 0.43-0.52 of the pipe:
@@ -1008,12 +893,12 @@ __global__ __launch_bounds__(64 * (PXB * CG + 1)) void conv3x3_s2p_kernel(Conv3A
     // residual and result through buffer descriptors of the view: a lane offset per unit, the channel in the scalar offset -- all
     // 40 residual loads in flight at once (one HBM round trip per tile; 64-bit addresses would cost 80 registers)
     const int po4 = Ho * Wo * 4, cb0 = cgrp * (CT16 * 16) + 4 * eg;     // Cout % 80 == 0: every channel tile of a group exists
-    const __amdgpu_buffer_rsrc_t ors = frag_rsrc(A.out + (size_t)n * A.out_ns + A.out_off, 0xffffffffu);
+    const __amdgpu_buffer_rsrc_t ors = frag_rsrc(A.out + A.omap.at(n, 0, 0, 0), 0xffffffffu);
     int rvo[2], ovo[2];
 #pragma unroll
     for (int u = 0; u < 2; ++u) {
       rvo[u] = cb0 * po4 + ((yo0 + ey[u]) * Wo + ex[u]) * 4;
-      ovo[u] = (cb0 * A.out_cs + (yo0 + ey[u]) * A.out_rs + ex[u]) * 4;
+      ovo[u] = (cb0 * A.omap.cs + (yo0 + ey[u]) * A.omap.rs + ex[u]) * 4;
     }
     float rv[CT16][4][2];
     if (A.res) {
@@ -1041,7 +926,7 @@ __global__ __launch_bounds__(64 * (PXB * CG + 1)) void conv3x3_s2p_kernel(Conv3A
         for (int u = 0; u < 2; ++u) {
           float v = fmaf(acc[c][u][e], (&sc.x)[e], (&sh.x)[e]);
           if (A.relu) v = relu_nan(v);
-          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v + rv[c][e][u]), ors, ovo[u], (16 * c + e) * A.out_cs * 4, 0);
+          __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v + rv[c][e][u]), ors, ovo[u], (16 * c + e) * A.omap.cs * 4, 0);
         }
     }
   }
@@ -1083,11 +968,11 @@ static int conv3x3_s2_shape(int Cout, int H, int W) {
 
 extern "C" hipError_t poem_launch_conv3x3_down2(const float* in, const void* wp, const float* scale, const float* shift,
                                                 const float* res, float* out, int views, int Cin, int Cout, int H, int W,
-                                                int relu, long out_ns, int out_cs, int out_rs, int out_off, hipStream_t s) {
+                                                int relu, ConvMap omap, hipStream_t s) {
   const int shape = conv3x3_s2_shape(Cout, H, W);
   if (!shape || Cin % 8) return hipErrorNotSupported;
   Conv3Args a{nullptr, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Cin)), scale, shift, res, out, Cin, Cout,
-              H, W, 2, relu, out_ns, out_cs, out_rs, out_off, views, nullptr, in, 0, Cin};
+              H, W, 2, relu, omap, views, nullptr, in, 0, Cin};
   const int RS = W / 2 + 1, tplane = 17 * 2 * RS, tstride = ((tplane + 63) & ~63) + 16;
   const size_t lds = (size_t)2 * 8 * tstride * sizeof(float);
   static std::atomic<unsigned long long> optin[6];
@@ -1186,12 +1071,11 @@ static hipError_t launch_conv3x3_lds(const Conv3Args& a, hipStream_t s) {
 // hipErrorNotSupported: the caller runs poem_launch_upcat_pad + poem_launch_conv3x3 instead.
 extern "C" hipError_t poem_launch_upcat_conv3x3(const float* a_half, int Ca, const float* b_full, int Cb, const void* wp,
                                                 const float* scale, const float* shift, float* out, int views, int Cout,
-                                                int H, int W, int relu, long out_ns, int out_cs, int out_rs, int out_off,
-                                                hipStream_t s) {
+                                                int H, int W, int relu, ConvMap omap, hipStream_t s) {
   if (Ca % 8 || Cb % 8 || Ca + Cb <= 0 || H % 2 || W % 2 || !conv3x3_lds_ok(Cout, H, W) || (long)(H / 2) * (W / 2) >= (1 << 20))
     return hipErrorNotSupported;
   Conv3Args a{nullptr, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Ca + Cb)), scale, shift, nullptr, out,
-              Ca + Cb, Cout, H, W, 1, relu, out_ns, out_cs, out_rs, out_off, views, a_half, b_full, Ca, Cb};
+              Ca + Cb, Cout, H, W, 1, relu, omap, views, a_half, b_full, Ca, Cb};
   return launch_conv3x3_lds<true>(a, s);
 }
 
@@ -1208,7 +1092,7 @@ extern "C" hipError_t poem_launch_upcat_conv3x3_pool_head(const float* a_half, i
   const size_t lds16 = (size_t)2 * 8 * tstride * sizeof(float);
   if ((size_t)(Cout * 4 * 32 + J * Cout + J) * sizeof(float) > lds16) return hipErrorNotSupported;
   Conv3Args a{nullptr, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Ca + Cb)), scale, shift, nullptr, nullptr,
-              Ca + Cb, Cout, H, W, 1, relu, 0, 0, 0, 0, views, a_half, b_full, Ca, Cb, head_w, head_b, hmap, J};
+              Ca + Cb, Cout, H, W, 1, relu, ConvMap(), views, a_half, b_full, Ca, Cb, head_w, head_b, hmap, J};
   hipLaunchKernelGGL((conv3x3_lds16_kernel<3, true, 64, true>), dim3((unsigned)(views * (H / TR))), dim3(512), lds16, s, a);
   return hipGetLastError();
 }
@@ -1226,8 +1110,7 @@ static hipError_t launch_conv3x3_any(const Conv3Args& a, hipStream_t s) {
   if (stride == 1 && conv3x3_lds_ok(Cout, H, W)) return launch_conv3x3_lds<false, EX>(a, s);
   const int pt = (ptiles % 2 == 0) ? 2 : 1;
   const int ct = (cot % 5 == 0) ? 5 : (cot % 3 == 0) ? 3 : (cot % 2 == 0) ? 2 : 1;
-  const long items = (long)views * (cot / ct) * (ptiles / pt);
-  const dim3 grid((unsigned)((items + 3) / 4)), block(256);
+  const dim3 grid = conv_item_grid((long)views * (cot / ct) * (ptiles / pt)), block(256);
 #define POEM_CONV(CTV, PTV) hipLaunchKernelGGL((conv3x3_kernel<CTV, PTV, EX>), grid, block, 0, s, a)
   if (pt == 2) {
     if (ct == 5) POEM_CONV(5, 2); else if (ct == 3) POEM_CONV(3, 2); else if (ct == 2) POEM_CONV(2, 2); else POEM_CONV(1, 2);
@@ -1240,29 +1123,33 @@ static hipError_t launch_conv3x3_any(const Conv3Args& a, hipStream_t s) {
 
 extern "C" hipError_t poem_launch_conv3x3(const float* in, const void* wp, const float* scale, const float* shift,
                                           const float* res, float* out, int views, int Cin, int Cout, int H, int W,
-                                          int stride, int relu, long out_ns, int out_cs, int out_rs, int out_off,
-                                          hipStream_t s) {
+                                          int stride, int relu, ConvMap omap, hipStream_t s) {
   if (Cin % 8) return hipErrorInvalidValue;
   Conv3Args a{in, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Cin)), scale, shift, res, out, Cin, Cout, H, W,
-              stride, relu, out_ns, out_cs, out_rs, out_off, views, nullptr, nullptr, 0, 0};
+              stride, relu, omap, views, nullptr, nullptr, 0, 0};
   return launch_conv3x3_any<false>(a, s);
 }
 
 // poem_launch_conv3x3 with the residual by its own (view, channel, row, offset) strides, before (res_pre) or after the activation
 extern "C" hipError_t poem_launch_conv3x3_ex(const float* in, const void* wp, const float* scale, const float* shift,
-                                             const float* res, long res_ns, int res_cs, int res_rs, int res_off, int res_pre,
+                                             const float* res, ConvMap rmap, int res_pre,
                                              float* out, int views, int Cin, int Cout, int H, int W, int stride, int relu,
-                                             long out_ns, int out_cs, int out_rs, int out_off, hipStream_t s) {
+                                             ConvMap omap, hipStream_t s) {
   if (Cin % 8) return hipErrorInvalidValue;
   Conv3Args a{in, (const float4*)wp, (const float2*)((const float*)wp + conv3x3_floats32(Cout, Cin)), scale, shift, res, out, Cin, Cout, H, W,
-              stride, relu, out_ns, out_cs, out_rs, out_off, views, nullptr, nullptr, 0, 0};
+              stride, relu, omap, views, nullptr, nullptr, 0, 0};
   a.res_pre = res_pre != 0;
-  a.res_ns = res_ns; a.res_cs = res_cs; a.res_rs = res_rs; a.res_off = res_off;
+  a.rmap = rmap;
   return launch_conv3x3_any<true>(a, s);
 }
 
 // out (views, Ca + Cb, H + 2 pad, W + 2 pad): channels [0, Ca) = bilinear x2 (align_corners=False) of a (views, Ca, H/2, W/2),
 // channels [Ca, Ca + Cb) = b (views, Cb, H, W), border = 0.  Ca or Cb may be 0 (pure upsample / pure pad).
+// STAGED = false nests the two directions of the interpolation as torch does; true evaluates it as Conv3Stager does while
+// poem_upcat_conv3x3 stages its input -- the four tap weights multiplied out, then one multiply and three fmas, which rounds
+// differently in the last place -- so that poem_conv3x3 of this tensor runs the same matrix instructions on the same operands as
+// poem_upcat_conv3x3: the two routes of the non-HRNet decode branch give the same bits.
+template <bool STAGED>
 __global__ void upcat_pad_kernel(const float* __restrict__ a, int Ca, const float* __restrict__ b, int Cb,
                                  float* __restrict__ out, int H, int W, int pad, long total) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1278,14 +1165,9 @@ __global__ void upcat_pad_kernel(const float* __restrict__ a, int Ca, const floa
   float v = 0.f;
   if (x >= 0 && x < W && y >= 0 && y < H) {
     if (c < Ca) {
-      // F.interpolate(scale_factor=2, mode='bilinear', align_corners=False): src = (dst + 0.5) / 2 - 0.5, clamped at 0
       const int h2 = H / 2, w2 = W / 2;
-      const float sy = fmaxf((y + 0.5f) * 0.5f - 0.5f, 0.f), sx = fmaxf((x + 0.5f) * 0.5f - 0.5f, 0.f);
-      const int y0 = (int)sy, x0 = (int)sx;
-      const int y1 = min(y0 + 1, h2 - 1), x1 = min(x0 + 1, w2 - 1);
-      const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
       const float* p = a + ((size_t)n * Ca + c) * h2 * w2;
-      v = hy * (hx * p[y0 * w2 + x0] + lx * p[y0 * w2 + x1]) + ly * (hx * p[y1 * w2 + x0] + lx * p[y1 * w2 + x1]);
+      v = STAGED ? up2_staged(p, w2, up2_tap(y, h2), up2_tap(x, w2)) : up2_nested(p, w2, up2_tap(y, h2), up2_tap(x, w2));
     } else {
       v = b[(((size_t)n * Cb + (c - Ca)) * H + y) * W + x];
     }
@@ -1297,7 +1179,16 @@ extern "C" hipError_t poem_launch_upcat_pad(const float* a, int Ca, const float*
                                             int W, int pad, hipStream_t s) {
   if ((Ca && (H % 2 || W % 2)) || pad < 0 || pad > 1 || Ca + Cb <= 0) return hipErrorInvalidValue;
   const long total = (long)views * (Ca + Cb) * (H + 2 * pad) * (W + 2 * pad);
-  hipLaunchKernelGGL(upcat_pad_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, Ca, b, Cb, out, H, W, pad, total);
+  hipLaunchKernelGGL(upcat_pad_kernel<false>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, Ca, b, Cb, out, H, W, pad, total);
+  return hipGetLastError();
+}
+
+extern "C" hipError_t poem_launch_upcat_pad_staged(const float* a, int Ca, const float* b, int Cb, float* out, int views, int H, int W,
+                                                   hipStream_t s) {
+  if ((Ca && (H % 2 || W % 2)) || Ca + Cb <= 0) return hipErrorInvalidValue;
+  const long total = (long)views * (Ca + Cb) * (H + 2) * (W + 2);
+  if ((total + 255) / 256 > 0x7fffffffL) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(upcat_pad_kernel<true>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, a, Ca, b, Cb, out, H, W, 1, total);
   return hipGetLastError();
 }
 
@@ -1352,13 +1243,7 @@ __global__ __launch_bounds__(NW * 64) void conv1x1_up2_kernel(const float* __res
   float* dst = out + (size_t)v * C * (4 * HW);
   for (int i = tid; i < C * 4 * HW; i += NW * 64) {
     const int c = i >> 8, y = (i >> 4) & 15, x = i & 15;
-    // F.interpolate(scale_factor=2, mode='bilinear', align_corners=False): src = (dst + 0.5) / 2 - 0.5, clamped at 0
-    const float sy = fmaxf((y + 0.5f) * 0.5f - 0.5f, 0.f), sx = fmaxf((x + 0.5f) * 0.5f - 0.5f, 0.f);
-    const int y0 = (int)sy, x0 = (int)sx;
-    const int y1 = min(y0 + 1, SIDE - 1), x1 = min(x0 + 1, SIDE - 1);
-    const float ly = sy - (float)y0, lx = sx - (float)x0, hy = 1.f - ly, hx = 1.f - lx;
-    const float* p = ytile + c * HW;
-    dst[i] = hy * (hx * p[y0 * SIDE + x0] + lx * p[y0 * SIDE + x1]) + ly * (hx * p[y1 * SIDE + x0] + lx * p[y1 * SIDE + x1]);
+    dst[i] = up2_nested(ytile + c * HW, SIDE, up2_tap(y, SIDE), up2_tap(x, SIDE));
   }
 }
 

@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "chain.h"
+#include "conv.h"
 #include "loss.h"
 #include "merge.h"
 
@@ -139,40 +140,29 @@ hipError_t poem_launch_heatmap_uv_conf(const float* hmap, float* uv, float* conf
                                        float img_h, hipStream_t s);
 size_t poem_conv3x3_packed_floats(int Cout, int Cin);
 hipError_t poem_launch_upcat_conv3x3(const float* a_half, int Ca, const float* b_full, int Cb, const void* wp, const float* scale,
-                                     const float* shift, float* out, int views, int Cout, int H, int W, int relu, long out_ns,
-                                     int out_cs, int out_rs, int out_off, hipStream_t s);
+                                     const float* shift, float* out, int views, int Cout, int H, int W, int relu, ConvMap omap,
+                                     hipStream_t s);
 hipError_t poem_launch_pack_conv3x3(const float* w, int Cout, int Cin, void* out, hipStream_t s);
 hipError_t poem_launch_conv3x3(const float* in, const void* wp, const float* scale, const float* shift, const float* res,
-                               float* out, int views, int Cin, int Cout, int H, int W, int stride, int relu, long out_ns,
-                               int out_cs, int out_rs, int out_off, hipStream_t s);
+                               float* out, int views, int Cin, int Cout, int H, int W, int stride, int relu, ConvMap omap,
+                               hipStream_t s);
 hipError_t poem_launch_conv3x3_ex(const float* in, const void* wp, const float* scale, const float* shift, const float* res,
-                                  long res_ns, int res_cs, int res_rs, int res_off, int res_pre, float* out, int views, int Cin,
-                                  int Cout, int H, int W, int stride, int relu, long out_ns, int out_cs, int out_rs, int out_off,
-                                  hipStream_t s);
+                                  ConvMap rmap, int res_pre, float* out, int views, int Cin, int Cout, int H, int W, int stride,
+                                  int relu, ConvMap omap, hipStream_t s);
 size_t poem_conv1x1_packed_floats(int Cout, int Cin);
 hipError_t poem_launch_pack_conv1x1(const float* w, int Cout, int Cin, void* out, hipStream_t s);
-hipError_t poem_launch_conv1x1_nchw(const float* in, long in_ns, int in_cs, int in_rs, int in_off, const void* wp,
-                                    const float* shift, const float* res, long res_ns, int res_cs, int res_rs, int res_off,
-                                    float* out, long out_ns, int out_cs, int out_rs, int out_off, int views, int Cin, int Cout,
-                                    int H, int W, int relu, hipStream_t s);
-hipError_t poem_launch_hrnet_fuse(const float* const* ptrs, const long* ns, const int* cs, const int* rs, const int* off,
-                                  const int* shift, int nterms, float* out, long out_ns, int out_cs, int out_rs, int out_off,
-                                  int views, int C, int H, int W, hipStream_t s);
+hipError_t poem_launch_conv1x1_nchw(const Conv1Args* a, hipStream_t s);
+hipError_t poem_launch_hrnet_fuse(const FuseArgs* a, hipStream_t s);
 // csrc/resnet.hip
 size_t poem_conv7x7_packed_floats(int Cout);
 hipError_t poem_launch_pack_conv7x7(const float* w, int Cout, void* out, hipStream_t s);
-hipError_t poem_launch_conv7x7_s2(const float* in, const void* wp, const float* scale, const float* shift, float* out, long out_ns,
-                                  int out_cs, int out_rs, int out_off, int views, int Cout, int H, int W, hipStream_t s);
-hipError_t poem_launch_maxpool3x3_s2(const float* in, long in_ns, int in_cs, int in_rs, int in_off, float* out, long out_ns,
-                                     int out_cs, int out_rs, int out_off, int views, int C, int H, int W, hipStream_t s);
+hipError_t poem_launch_conv7x7_s2(const StemArgs* a, hipStream_t s);
+hipError_t poem_launch_maxpool3x3_s2(const PoolArgs* a, hipStream_t s);
 hipError_t poem_launch_upcat_pad_staged(const float* a, int Ca, const float* b, int Cb, float* out, int views, int H, int W,
                                         hipStream_t s);
-hipError_t poem_launch_sconv1x1(const float* in, long in_ns, int in_cs, int in_rs, int in_off, const void* wp, const float* shift,
-                                float* out, long out_ns, int out_cs, int out_rs, int out_off, int views, int Cin, int Cout, int H,
-                                int W, int pool, int act, hipStream_t s);
+hipError_t poem_launch_sconv1x1(const SConvArgs* a, hipStream_t s);
 hipError_t poem_launch_conv3x3_down2(const float* in, const void* wp, const float* scale, const float* shift, const float* res,
-                                     float* out, int views, int Cin, int Cout, int H, int W, int relu, long out_ns, int out_cs,
-                                     int out_rs, int out_off, hipStream_t s);
+                                     float* out, int views, int Cin, int Cout, int H, int W, int relu, ConvMap omap, hipStream_t s);
 void poem_decode_s2_staging_wave(int on);
 void poem_decode_row_stager(int on);
 void poem_decode_pin32(int on);

@@ -285,14 +285,14 @@ int poem_conv3x3(const float* in_padded, const void* w_packed, const float* scal
   if ((stride != 1 && stride != 2) || h <= 0 || w <= 0 || h % stride || w % stride || ((h / stride) * (w / stride)) % 32)
     return POEM_E_UNSUPPORTED;
   HIPCHK(poem_launch_conv3x3(in_padded, w_packed, scale, shift, residual, out, views, cin, cout, h, w, stride, relu,
-                             (long)out_view_stride, out_ch_stride, out_row_stride, out_offset, (hipStream_t)stream));
+                             ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset), (hipStream_t)stream));
   return POEM_OK;
 }
 
-// (n, c, y, x) -> p[n * vs + c * cs + y * rs + x + off] stays inside the view's c * cs floats for every channel: a plain map or
-// the interior of a bordered one (the kernels read the input through a per-view buffer descriptor of that size)
-static bool map_ok(int64_t vs, int cs, int rs, int off, int h, int w) {
-  return vs >= 0 && cs > 0 && rs >= w && off >= 0 && (int64_t)(h - 1) * rs + (w - 1) + off < (int64_t)cs;
+// an (h, w) map stays inside the view's c * cs floats for every channel: a plain map or the interior of a bordered one (the
+// kernels read the input through a per-view buffer descriptor of that size)
+static bool map_ok(const ConvMap& m, int h, int w) {
+  return m.ns >= 0 && m.cs > 0 && m.rs >= w && m.off >= 0 && (int64_t)(h - 1) * m.rs + (w - 1) + m.off < (int64_t)m.cs;
 }
 
 int poem_conv3x3_ex(const float* in_padded, const void* w_packed, const float* scale, const float* shift, const float* residual,
@@ -303,11 +303,12 @@ int poem_conv3x3_ex(const float* in_padded, const void* w_packed, const float* s
   if ((stride != 1 && stride != 2) || h <= 0 || w <= 0 || h % stride || w % stride || ((h / stride) * (w / stride)) % 32)
     return POEM_E_UNSUPPORTED;
   if ((uint64_t)cin * (uint64_t)(h + 2) * (uint64_t)(w + 2) * 4 >= (1ull << 31)) return POEM_E_UNSUPPORTED;
-  if (residual && !map_ok(res_view_stride, res_ch_stride, res_row_stride, res_offset, h / stride, w / stride)) return POEM_E_ARG;
-  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / stride, w / stride)) return POEM_E_ARG;
-  HIPCHK(poem_launch_conv3x3_ex(in_padded, w_packed, scale, shift, residual, (long)res_view_stride, res_ch_stride, res_row_stride,
-                                res_offset, res_before_act, out, views, cin, cout, h, w, stride, relu, (long)out_view_stride,
-                                out_ch_stride, out_row_stride, out_offset, (hipStream_t)stream));
+  const ConvMap rmap((long)res_view_stride, res_ch_stride, res_row_stride, res_offset);
+  const ConvMap omap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset);
+  if (residual && !map_ok(rmap, h / stride, w / stride)) return POEM_E_ARG;
+  if (!map_ok(omap, h / stride, w / stride)) return POEM_E_ARG;
+  HIPCHK(poem_launch_conv3x3_ex(in_padded, w_packed, scale, shift, residual, rmap, res_before_act, out, views, cin, cout, h, w, stride,
+                                relu, omap, (hipStream_t)stream));
   return POEM_OK;
 }
 
@@ -328,32 +329,35 @@ int poem_conv1x1(const float* in, int64_t in_view_stride, int in_ch_stride, int 
                  int views, int cin, int cout, int h, int w, int relu, void* stream) {
   if (!in || !w_packed || !out || views <= 0 || cin <= 0 || cin % 8 || cout <= 0) return POEM_E_ARG;
   if (h <= 0 || w <= 0 || ((int64_t)h * w) % 32 || (int64_t)h * w >= (1ll << 29)) return POEM_E_UNSUPPORTED;
-  if (!map_ok(in_view_stride, in_ch_stride, in_row_stride, in_offset, h, w)) return POEM_E_ARG;
+  const Conv1Args a{in, (const float4*)w_packed, shift, residual, out,
+                    ConvMap((long)in_view_stride, in_ch_stride, in_row_stride, in_offset),
+                    ConvMap((long)res_view_stride, res_ch_stride, res_row_stride, res_offset),
+                    ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset), cin, cout, h, w, relu, views};
+  if (!map_ok(a.imap, h, w)) return POEM_E_ARG;
   if ((uint64_t)cin * (uint64_t)in_ch_stride * 4 >= (1ull << 31)) return POEM_E_UNSUPPORTED;
-  if (residual && !map_ok(res_view_stride, res_ch_stride, res_row_stride, res_offset, h, w)) return POEM_E_ARG;
-  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h, w)) return POEM_E_ARG;
-  HIPCHK(poem_launch_conv1x1_nchw(in, (long)in_view_stride, in_ch_stride, in_row_stride, in_offset, w_packed, shift, residual,
-                                  (long)res_view_stride, res_ch_stride, res_row_stride, res_offset, out, (long)out_view_stride,
-                                  out_ch_stride, out_row_stride, out_offset, views, cin, cout, h, w, relu, (hipStream_t)stream));
+  if (residual && !map_ok(a.rmap, h, w)) return POEM_E_ARG;
+  if (!map_ok(a.omap, h, w)) return POEM_E_ARG;
+  HIPCHK(poem_launch_conv1x1_nchw(&a, (hipStream_t)stream));
   return POEM_OK;
 }
 
 int poem_hrnet_fuse(const poem_fuse_term_t* terms, int nterms, float* out, int64_t out_view_stride, int out_ch_stride,
                     int out_row_stride, int out_offset, int views, int channels, int h, int w, void* stream) {
   if (!terms || !out || nterms < 2 || nterms > 4 || views <= 0 || channels <= 0 || h <= 0 || w <= 0) return POEM_E_ARG;
-  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h, w)) return POEM_E_ARG;
-  const float* ptrs[4];
-  long ns[4];
-  int cs[4], rs[4], off[4], shift[4];
+  FuseArgs a{};
+  a.nterms = nterms;
+  a.out = out;
+  a.omap = ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset);
+  a.C = channels; a.H = h; a.W = w; a.views = views;
+  if (!map_ok(a.omap, h, w)) return POEM_E_ARG;
   for (int k = 0; k < nterms; ++k) {
     const poem_fuse_term_t& t = terms[k];
     if (!t.data || t.shift < 0 || t.shift > 3) return POEM_E_ARG;
-    if (!map_ok(t.view_stride, t.ch_stride, t.row_stride, t.offset, ((h - 1) >> t.shift) + 1, ((w - 1) >> t.shift) + 1)) return POEM_E_ARG;
-    ptrs[k] = t.data; ns[k] = (long)t.view_stride; cs[k] = t.ch_stride; rs[k] = t.row_stride; off[k] = t.offset; shift[k] = t.shift;
+    a.t[k] = FuseTerm{t.data, ConvMap((long)t.view_stride, t.ch_stride, t.row_stride, t.offset), t.shift};
+    if (!map_ok(a.t[k].map, ((h - 1) >> t.shift) + 1, ((w - 1) >> t.shift) + 1)) return POEM_E_ARG;
   }
   if ((int64_t)views * channels * h * w > (int64_t)0x7fffffff * 256) return POEM_E_UNSUPPORTED;
-  HIPCHK(poem_launch_hrnet_fuse(ptrs, ns, cs, rs, off, shift, nterms, out, (long)out_view_stride, out_ch_stride, out_row_stride,
-                                out_offset, views, channels, h, w, (hipStream_t)stream));
+  HIPCHK(poem_launch_hrnet_fuse(&a, (hipStream_t)stream));
   return POEM_OK;
 }
 
@@ -377,9 +381,10 @@ int poem_conv7x7_s2(const float* in, const void* w_packed, const float* scale, c
                     void* stream) {
   if (!in || !w_packed || !scale || !shift || !out || views <= 0 || cout <= 0) return POEM_E_ARG;
   if (!half_tiles(h, w) || cout % 32 || (uint64_t)3 * (uint64_t)h * (uint64_t)w * 4 >= (1ull << 31)) return POEM_E_UNSUPPORTED;
-  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / 2, w / 2)) return POEM_E_ARG;
-  HIPCHK(poem_launch_conv7x7_s2(in, w_packed, scale, shift, out, (long)out_view_stride, out_ch_stride, out_row_stride, out_offset,
-                                views, cout, h, w, (hipStream_t)stream));
+  const StemArgs a{in, (const float4*)w_packed, scale, shift, out,
+                   ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset), cout, h, w, views};
+  if (!map_ok(a.omap, h / 2, w / 2)) return POEM_E_ARG;
+  HIPCHK(poem_launch_conv7x7_s2(&a, (hipStream_t)stream));
   return POEM_OK;
 }
 
@@ -388,11 +393,12 @@ int poem_maxpool3x3_s2(const float* in, int64_t in_view_stride, int in_ch_stride
                        int w, void* stream) {
   if (!in || !out || views <= 0 || channels <= 0) return POEM_E_ARG;
   if (h <= 0 || w <= 0 || h % 2 || w % 2) return POEM_E_UNSUPPORTED;
-  if (!map_ok(in_view_stride, in_ch_stride, in_row_stride, in_offset, h, w)) return POEM_E_ARG;
-  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / 2, w / 2)) return POEM_E_ARG;
+  const PoolArgs a{in, out, ConvMap((long)in_view_stride, in_ch_stride, in_row_stride, in_offset),
+                   ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset), channels, h, w, views};
+  if (!map_ok(a.imap, h, w)) return POEM_E_ARG;
+  if (!map_ok(a.omap, h / 2, w / 2)) return POEM_E_ARG;
   if ((int64_t)views * channels * (h / 2) * (w / 2) > (int64_t)0x7fffffff * 256) return POEM_E_UNSUPPORTED;
-  HIPCHK(poem_launch_maxpool3x3_s2(in, (long)in_view_stride, in_ch_stride, in_row_stride, in_offset, out, (long)out_view_stride,
-                                   out_ch_stride, out_row_stride, out_offset, views, channels, h, w, (hipStream_t)stream));
+  HIPCHK(poem_launch_maxpool3x3_s2(&a, (hipStream_t)stream));
   return POEM_OK;
 }
 
@@ -401,11 +407,11 @@ int poem_conv1x1_s2(const float* in, int64_t in_view_stride, int in_ch_stride, i
                     int views, int cin, int cout, int h, int w, void* stream) {
   if (!in || !w_packed || !out || views <= 0 || cin <= 0 || cin % 8 || cout <= 0) return POEM_E_ARG;
   if (!half_tiles(h, w)) return POEM_E_UNSUPPORTED;
-  if (!map_ok(in_view_stride, in_ch_stride, in_row_stride, in_offset, h, w)) return POEM_E_ARG;
-  if (!map_ok(out_view_stride, out_ch_stride, out_row_stride, out_offset, h / 2, w / 2)) return POEM_E_ARG;
-  HIPCHK(poem_launch_sconv1x1(in, (long)in_view_stride, in_ch_stride, in_row_stride, in_offset, w_packed, shift, out,
-                              (long)out_view_stride, out_ch_stride, out_row_stride, out_offset, views, cin, cout, h, w, 0, 0,
-                              (hipStream_t)stream));
+  const SConvArgs a{in, (const float4*)w_packed, shift, out, ConvMap((long)in_view_stride, in_ch_stride, in_row_stride, in_offset),
+                    ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset), cin, cout, h, w, 0, 0, views};
+  if (!map_ok(a.imap, h, w)) return POEM_E_ARG;
+  if (!map_ok(a.omap, h / 2, w / 2)) return POEM_E_ARG;
+  HIPCHK(poem_launch_sconv1x1(&a, (hipStream_t)stream));
   return POEM_OK;
 }
 
@@ -420,8 +426,8 @@ int poem_maxpool2_conv1x1(const float* x, const void* w_packed, const float* bia
                           int w, int act, void* stream) {
   if (!x || !w_packed || !bias || !out || views <= 0 || cin <= 0 || cin % 8 || cout <= 0 || act < 0 || act > 1) return POEM_E_ARG;
   if (!half_tiles(h, w) || (int64_t)h * w >= (1ll << 31)) return POEM_E_UNSUPPORTED;
-  HIPCHK(poem_launch_sconv1x1(x, (long)cin * h * w, h * w, w, 0, w_packed, bias, out, (long)cout * (h / 2) * (w / 2), (h / 2) * (w / 2),
-                              w / 2, 0, views, cin, cout, h, w, 1, act, (hipStream_t)stream));
+  const SConvArgs a{x, (const float4*)w_packed, bias, out, ConvMap(cin, h, w), ConvMap(cout, h / 2, w / 2), cin, cout, h, w, 1, act, views};
+  HIPCHK(poem_launch_sconv1x1(&a, (hipStream_t)stream));
   return POEM_OK;
 }
 
@@ -430,7 +436,8 @@ int poem_conv3x3_down2(const float* in, const void* w_packed, const float* scale
                        int out_ch_stride, int out_row_stride, int out_offset, void* stream) {
   if (!in || !w_packed || !scale || !shift || !out || views <= 0 || cin <= 0 || cout <= 0 || h <= 0 || w <= 0) return POEM_E_ARG;
   const hipError_t e = poem_launch_conv3x3_down2(in, w_packed, scale, shift, residual, out, views, cin, cout, h, w, relu,
-                                                 (long)out_view_stride, out_ch_stride, out_row_stride, out_offset, (hipStream_t)stream);
+                                                 ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset),
+                                                 (hipStream_t)stream);
   if (e == hipErrorNotSupported) return POEM_E_UNSUPPORTED;
   HIPCHK(e);
   return POEM_OK;
@@ -442,7 +449,8 @@ int poem_upcat_conv3x3(const float* a_half, int ca, const float* b_full, int cb,
   if ((!a_half && ca) || (!b_full && cb) || !w_packed || !scale || !shift || !out || views <= 0 || cout <= 0 || h <= 0 || w <= 0)
     return POEM_E_ARG;
   const hipError_t e = poem_launch_upcat_conv3x3(a_half, ca, b_full, cb, w_packed, scale, shift, out, views, cout, h, w, relu,
-                                                 (long)out_view_stride, out_ch_stride, out_row_stride, out_offset, (hipStream_t)stream);
+                                                 ConvMap((long)out_view_stride, out_ch_stride, out_row_stride, out_offset),
+                                                 (hipStream_t)stream);
   if (e == hipErrorNotSupported) return POEM_E_UNSUPPORTED;
   HIPCHK(e);
   return POEM_OK;

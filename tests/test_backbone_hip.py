@@ -179,7 +179,7 @@ def _conv1_ref(x, wt, shift, res, relu, dtype):
 
 
 @pytest.mark.parametrize("h,w", [(4, 8), (16, 16)])
-@pytest.mark.parametrize("cin,cout", [(64, 64), (256, 64), (64, 256), (320, 40), (80, 40)])
+@pytest.mark.parametrize("cin,cout", [(64, 64), (256, 64), (64, 256), (320, 40), (80, 40), (40, 32), (8, 96), (24, 160)])
 def test_conv1x1(cin, cout, h, w):
     views = 3
     g = torch.Generator().manual_seed(cin + 7 * cout + h)

@@ -17,7 +17,7 @@ where the entry point can refuse, that the library's taken / POEM_E_UNSUPPORTED 
     conv3x3_s2_kernel<8,1,18> <4,2,10> <2,4,5>      two and three tiles under s2_staging_wave 1/2/3/4 against 0       test_down2_many_tiles
     conv1x1_up2_kernel<10>                          (K, C) (8,32) (40,160) (8,192: 12 jobs, 10 waves) (448,192: LDS)  test_conv1x1_upsample2
     pool_head_kernel                                (C, J) (1,1) (40,21) (64,32) on 2x2 and 6x10                      test_pool_conv1x1_sigmoid
-    upcat_pad_kernel / upcat_pad_staged_kernel      the two-launch side of every fused case                          test_upcat_conv3x3
+    upcat_pad_kernel<false> / <true> (staged)       the two-launch side of every fused case                          test_upcat_conv3x3
     every family, NaN / +Inf in the input           one case each, both stagers, both pools, both stride-2 kernels    test_non_finite_inputs
     FeatureDecoders (HRNet, resnet34)               a NaN in the finest and in the coarsest level, all routes          test_decoders_keep_a_nan
 
