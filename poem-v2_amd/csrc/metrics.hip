@@ -8,7 +8,8 @@
 // PAEval.align_w_scale (lib/metrics/pa_eval.py:104-124): centre both point sets, scale each to unit Frobenius norm
 // (+1e-8), R, s = scipy.linalg.orthogonal_procrustes(gt_n, pred_n)  [R = U V^T, s = sum(w) for gt_n^T pred_n = U w V^T;
 // no reflection handling -- exactly as upstream], aligned = pred_n R^T s * s_gt + mean_gt.
-// One wave per sample; the 3x3 polar factor comes from a fp64 Jacobi eigen-decomposition of M^T M.
+// One wave per sample; the 3x3 polar factor comes from a fp64 Jacobi eigen-decomposition of M^T M -- and, where a set is
+// flat or a line, so that a singular value vanishes, from M itself, so that R is orthogonal whenever M is not 0.
 // out[b] = (mean_i |aligned_i - gt_i|, mean_i |pred_i - gt_i|)          (get_dist, pa_eval.py:40-43)
 __device__ inline double wave_sum(double v) {
 #pragma unroll
@@ -59,15 +60,52 @@ __global__ __launch_bounds__(256) void pa_epe_kernel(const float* __restrict__ p
   }
   double w[3], scale = 0;
   for (int k = 0; k < 3; ++k) { w[k] = sqrt(fmax(S[k][k], 0.0)); scale += w[k]; }
-  // R = U V^T = M V diag(1/w) V^T   (3x3); a vanishing singular value leaves its direction out (degenerate input)
+  // R = U V^T = M V diag(1/w) V^T   (3x3)
   double MV[3][3], R[3][3];
   for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) { MV[r][c] = 0; for (int k = 0; k < 3; ++k) MV[r][c] += M[r][k] * V[k][c]; }
   const double wmax = fmax(w[0], fmax(w[1], w[2]));
-  for (int r = 0; r < 3; ++r)
-    for (int c = 0; c < 3; ++c) {
-      R[r][c] = 0;
-      for (int k = 0; k < 3; ++k) if (w[k] > 1e-14 * wmax) R[r][c] += MV[r][k] / w[k] * V[c][k];
+  int k3 = w[1] < w[0] ? 1 : 0;
+  if (w[2] < w[k3]) k3 = 2;
+  int k1 = (k3 + 1) % 3, k2 = (k3 + 2) % 3;
+  if (w[k2] > w[k1]) { const int t = k1; k1 = k2; k2 = t; }          // w[k1] >= w[k2] >= w[k3]
+  if (wmax > 0.0 && w[k3] < 1e-3 * wmax) {
+    // A flat point set (three points, a planar ground truth) or a line: M^T M squares the conditioning, so w[k3] has lost its
+    // digits -- or is 0 while the other set does extend along that direction.  R stays orthogonal, as scipy's is: the left
+    // vectors come from M itself (u = M v / |M v|, the second made orthogonal to the first; for rank 1 any unit vector across
+    // the first), the third pair is completed by cross products, and its sign and singular value are u3^T M v3, which keeps
+    // its sign down to rounding of M.  Where that value is exactly 0 either sign is an answer of upstream's.
+    double u1[3], u2[3], n1 = 0, n2 = 0, dot = 0;
+    for (int r = 0; r < 3; ++r) n1 += MV[r][k1] * MV[r][k1];
+    n1 = sqrt(n1);
+    for (int r = 0; r < 3; ++r) { u1[r] = MV[r][k1] / n1; dot += u1[r] * MV[r][k2]; }
+    for (int r = 0; r < 3; ++r) { u2[r] = MV[r][k2] - dot * u1[r]; n2 += u2[r] * u2[r]; }
+    n2 = sqrt(n2);
+    double un = n2;
+    if (!(n2 > 1e-12 * n1)) {
+      int m = fabs(u1[1]) < fabs(u1[0]) ? 1 : 0;
+      if (fabs(u1[2]) < fabs(u1[m])) m = 2;
+      un = 0;
+      for (int r = 0; r < 3; ++r) { u2[r] = (r == m ? 1.0 : 0.0) - u1[m] * u1[r]; un += u2[r] * u2[r]; }
+      un = sqrt(un);
     }
+    for (int r = 0; r < 3; ++r) u2[r] /= un;
+    const double u3[3] = {u1[1] * u2[2] - u1[2] * u2[1], u1[2] * u2[0] - u1[0] * u2[2], u1[0] * u2[1] - u1[1] * u2[0]};
+    const double v3[3] = {V[1][k1] * V[2][k2] - V[2][k1] * V[1][k2], V[2][k1] * V[0][k2] - V[0][k1] * V[2][k2],
+                          V[0][k1] * V[1][k2] - V[1][k1] * V[0][k2]};
+    double d3 = 0;
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 3; ++c) d3 += u3[r] * M[r][c] * v3[c];
+    const double sg = d3 < 0 ? -1.0 : 1.0;
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) R[r][c] = u1[r] * V[c][k1] + u2[r] * V[c][k2] + sg * u3[r] * v3[c];
+    scale = n1 + n2 + fabs(d3);
+  } else {
+    // well conditioned -- or M = 0 (a prediction that is one point), where R = 0 and scale = 0 put every point on the gt's mean
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 3; ++c) {
+        R[r][c] = 0;
+        for (int k = 0; k < 3; ++k) if (w[k] > 1e-14 * wmax) R[r][c] += MV[r][k] / w[k] * V[c][k];
+      }
+  }
   // aligned_i = (pred_c_i / s2) R^T * scale * s1 + mean_gt
   double dpa = 0, draw = 0;
   for (int i = lane; i < P; i += 64) {
@@ -110,7 +148,9 @@ __global__ void pck_accumulate_kernel(const float* __restrict__ pred, const floa
 #pragma clang fp contract(off)
       const float dx = p[0] - g[0], dy = p[1] - g[1], dz = p[2] - g[2];
       const float xx = dx * dx, yy = dy * dy, zz = dz * dz;
-      d = __fsqrt_rn((xx + yy) + zz);
+      // the correctly rounded root, as numpy's: through fp64, whose 53 bits make the second rounding harmless (__fsqrt_rn is
+      // the hardware's approximate v_sqrt_f32 here, which can be a place off)
+      d = (float)sqrt((double)((xx + yy) + zz));
     }
     acc += (double)d;
     if (dist_out) dist_out[(size_t)b * P + k] = d;
