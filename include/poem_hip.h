@@ -47,6 +47,8 @@
  *                             mlvl_feat and the per-view 2-D joints
  *   poem_pa_epe /             PAEval.feed + align_w_scale (lib/metrics/pa_eval.py:45-83,104-124) and _PCKMetric.feed
  *   poem_pck_accumulate       (lib/metrics/pck.py:36-96) -- device-side evaluation metrics
+ *   poem_pa_align /           align_w_scale (lib/metrics/pa_eval.py:104-124) with the aligned set kept, and the nearest-neighbour loop
+ *   poem_nn_distance          of the FreiHAND / HO3D protocol scripts (no upstream code): mesh F@5 / F@15, aligned AUC
  *   poem_mano_to_openpose     mano_to_openpose (lib/utils/transform.py:836-872) -- joints from mesh for the metrics (N3)
  *   poem_warp_affine          cv2.warpAffine + colour jitter + to_tensor / normalize of SimpleTransform2D.__call__
  *                             (lib/utils/transform.py:153-170) and the mirror warp of process_data_item
@@ -535,6 +537,32 @@ int poem_upcat_conv3x3_pool_head(const float* a_half, int ca, const float* b_ful
 int poem_pa_epe(const float* pred, const float* gt, float* out, int batch, int npoints, void* stream);
 int poem_pck_accumulate(const float* pred, const float* gt, int batch, int npoints, double val_min, double val_max,
                         int steps, uint32_t* counts, double* dist_sum, uint32_t* n, float* dist_out, void* stream);
+/* Benchmark-protocol mesh scores: the device pieces of the FreiHAND / HO3D numbers -- mesh F-scores at 5 / 15 mm, raw and
+ * Procrustes-aligned, and the AUC of the aligned joints / vertices.  The reference tree has no code of these (the public protocol
+ * scripts loop over samples on the host through open3d); what each call replaces upstream is named with it.
+ * poem_pa_align: PAEval.align_w_scale (lib/metrics/pa_eval.py:104-124) with its result kept: pred, gt (B,P,3) ->
+ *   aligned (B,P,3) fp32, the fp32 rounding of the fp64 points whose mean distance to gt poem_pa_epe reports (one solve behind
+ *   both), and transform (B,13) fp64 = c, R (3x3 row-major), t with aligned = c R p + t.  Either output may be NULL, not both.
+ * poem_nn_distance: for a (B,na,3) and b (B,nb,3) the distance of every point of a to its nearest point of b (dist_ab (B,na)) and of
+ *   every point of b to its nearest of a (dist_ba (B,nb)) -- the per-sample nearest-neighbour loop of the protocol scripts, brute
+ *   force, any na, nb up to 2^24.  Squares in fp32 in numpy's order ((dx*dx + dy*dy) + dz*dz), each operation rounded on its own; the
+ *   minimum over the fp32 squares; one root per point, of the minimum, correctly rounded (through fp64).
+ *   counts (B,2,nthr) int32 = #{(double)d < thresholds[t]} per direction (0: a -> b, 1: b -> a) -- STRICT `<`, as the protocol
+ *   scripts compare (poem_pck_accumulate's `<=` is _PCKMetric's) -- written, not accumulated; sums (B,2) fp64 = the distances'
+ *   sum.  Every output is optional (NULL), at least one is needed.  thresholds: nthr <= 8 doubles in HOST memory, read at the call,
+ *   non-negative and ascending; needed with counts.  counts and sums are reduced in a fixed order through `workspace`
+ *   (poem_nn_distance_workspace_bytes(batch, na, nb, nthr) bytes, 8-byte aligned; not read when both are NULL): no atomics, and a
+ *   sample's bits do not depend on the batch it is in.
+ *   NaN rule: a point with a NaN coordinate is nearest to nothing and nothing is nearest to it -- its own distance is NaN (NaN in
+ *   dist_*, counted under no threshold, carried by sums), it never lowers another point's minimum, and a direction whose target
+ *   set is all NaN gives NaN distances and zero counts.
+ *   POEM_E_ARG: NULL a / b, non-positive sizes, all four outputs NULL, counts without thresholds, a NaN, negative or non-ascending
+ *   threshold; POEM_E_UNSUPPORTED: na or nb above 2^24 (poem_render_mesh's limit on a point count), nthr > 8;
+ *   POEM_E_WORKSPACE: counts or sums asked for and the workspace NULL or short. */
+int poem_pa_align(const float* pred, const float* gt, float* aligned, double* transform, int batch, int npoints, void* stream);
+size_t poem_nn_distance_workspace_bytes(int batch, int na, int nb, int nthr);
+int poem_nn_distance(const float* a, int na, const float* b, int nb, float* dist_ab, float* dist_ba, const double* thresholds, int nthr,
+                     int32_t* counts, double* sums, void* workspace, size_t workspace_bytes, int batch, void* stream);
 /* mano_to_openpose (lib/utils/transform.py:836-872; called on predicted and ground-truth vertices by testing_step,
  * lib/models/POEM.py:602-603): j_regressor (16,nverts) MANO's th_J_regressor, verts (B,nverts,3) -> joints (B,21,3) in
  * OpenPose order (16 regressed joints + the 5 finger-tip vertices, re-ordered).  nverts must be 778. */

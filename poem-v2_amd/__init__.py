@@ -18,3 +18,5 @@ from .mano import ManoLayer  # noqa: F401
 from .hip import make_basis  # noqa: F401
 from .render import MeshRenderer, DrawingHandCallback, draw_skeleton, project_to_views, save_png  # noqa: F401
 from .losses import PoemLoss, LossMetric  # noqa: F401
+from . import metrics  # noqa: F401
+from .metrics import MeshFScore, PAJoint3DPCK, PAVert3DPCK, procrustes_align, nearest_distances  # noqa: F401

@@ -129,6 +129,10 @@ hipError_t poem_launch_dlt_confidence(const float* uv, const float* conf, const 
 hipError_t poem_launch_pa_epe(const float* pred, const float* gt, float* out, int B, int P, hipStream_t s);
 hipError_t poem_launch_pck_accumulate(const float* pred, const float* gt, int B, int P, double vmin, double vmax, int steps,
                                       unsigned int* counts, double* sum, unsigned int* n, float* dist_out, hipStream_t s);
+hipError_t poem_launch_pa_align(const float* pred, const float* gt, float* aligned, double* transform, int B, int P, hipStream_t s);
+size_t poem_nn_distance_slots(int B, int na, int nb);
+hipError_t poem_launch_nn_distance(const float* a, int na, const float* b, int nb, float* dist_ab, float* dist_ba,
+                                   const double* thr, int nthr, int* counts, double* sums, void* workspace, int B, hipStream_t s);
 hipError_t poem_launch_mano_to_openpose(const float* jreg, const float* verts, float* joints, int B, int nverts,
                                         hipStream_t s);
 hipError_t poem_launch_warp_affine(const unsigned char* src, const long long* src_off, const int* src_hw,

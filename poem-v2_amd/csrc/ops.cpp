@@ -517,6 +517,39 @@ int poem_pck_accumulate(const float* pred, const float* gt, int batch, int npoin
   return POEM_OK;
 }
 
+// ---- benchmark-protocol mesh scores (csrc/meshscore.hip) ---------------------------------------------------------------------------
+int poem_pa_align(const float* pred, const float* gt, float* aligned, double* transform, int batch, int npoints, void* stream) {
+  if (!pred || !gt || (!aligned && !transform) || batch <= 0 || npoints < 3 || ((uintptr_t)transform & 7)) return POEM_E_ARG;
+  HIPCHK(poem_launch_pa_align(pred, gt, aligned, transform, batch, npoints, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+// workspace of a search that reduces: one double and nthr ints per launched block (sample, direction, chunk of query points)
+size_t poem_nn_distance_workspace_bytes(int batch, int na, int nb, int nthr) {
+  if (batch <= 0 || na <= 0 || nb <= 0 || nthr < 0 || nthr > 8 || na > (1 << 24) || nb > (1 << 24)) return 0;
+  const size_t slots = poem_nn_distance_slots(batch, na, nb);
+  return (slots * (sizeof(double) + (size_t)nthr * sizeof(int32_t)) + 7) & ~(size_t)7;
+}
+
+int poem_nn_distance(const float* a, int na, const float* b, int nb, float* dist_ab, float* dist_ba, const double* thresholds,
+                     int nthr, int32_t* counts, double* sums, void* workspace, size_t workspace_bytes, int batch, void* stream) {
+  if (!a || !b || na <= 0 || nb <= 0 || batch <= 0 || nthr < 0) return POEM_E_ARG;
+  if (!dist_ab && !dist_ba && !counts && !sums) return POEM_E_ARG;
+  if (counts && (!thresholds || nthr <= 0)) return POEM_E_ARG;
+  if (((uintptr_t)sums & 7) || ((uintptr_t)workspace & 7)) return POEM_E_ARG;
+  if (na > (1 << 24) || nb > (1 << 24) || nthr > 8) return POEM_E_UNSUPPORTED;      // the renderer's limit on a point count
+  if (thresholds)
+    for (int k = 0; k < nthr; ++k)          // NaN, negative or not strictly ascending (`!(x >= 0)` is true of a NaN)
+      if (!(thresholds[k] >= 0.0) || (k > 0 && !(thresholds[k] > thresholds[k - 1]))) return POEM_E_ARG;
+  if (poem_nn_distance_slots(batch, na, nb) > 0x7fffffffu) return POEM_E_UNSUPPORTED;     // one block per slot: the grid's x limit
+  if (counts || sums) {
+    if (!workspace || workspace_bytes < poem_nn_distance_workspace_bytes(batch, na, nb, counts ? nthr : 0)) return POEM_E_WORKSPACE;
+  }
+  HIPCHK(poem_launch_nn_distance(a, na, b, nb, dist_ab, dist_ba, thresholds, counts ? nthr : 0, counts, sums, workspace, batch,
+                                 (hipStream_t)stream));
+  return POEM_OK;
+}
+
 int poem_mano_to_openpose(const float* j_regressor, const float* verts, float* joints, int batch, int nverts, void* stream) {
   if (!j_regressor || !verts || !joints || batch <= 0) return POEM_E_ARG;
   if (nverts != 778) return POEM_E_UNSUPPORTED;          // the tip vertex ids are MANO's

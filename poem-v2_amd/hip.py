@@ -124,6 +124,9 @@ SIGNATURES = {
     "poem_pool_conv1x1_sigmoid": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "poem_upcat_conv3x3_pool_head": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "poem_pa_epe": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    "poem_pa_align": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp]),
+    "poem_nn_distance_workspace_bytes": (_sz, [_i, _i, _i, _i]),
+    "poem_nn_distance": (_i, [_vp, _i, _vp, _i, _vp, _vp, ctypes.POINTER(ctypes.c_double), _i, _vp, _vp, _vp, _sz, _i, _vp]),
     "poem_mano_to_openpose": (_i, [_vp, _vp, _vp, _i, _i, _vp]),
     "poem_rot6d_to_axis_angle": (_i, [_vp, _vp, _vp, _i, _vp]),
     "poem_mano_table_bytes": (_sz, []),

@@ -228,3 +228,163 @@ def mano_to_openpose(J_regressor, mano_verts):
     hip.check(hip.lib().poem_mano_to_openpose(hip.ptr(w), hip.ptr(v), hip.ptr(out), v.shape[0], 778, hip.stream()),
               "poem_mano_to_openpose")
     return out
+
+
+# ---- benchmark-protocol mesh scores: F@5 / F@15 and the aligned AUC on the device -----------------
+def procrustes_align(pred, gt, return_transform=False):
+    """``PAEval.align_w_scale(gt, pred)`` (lib/metrics/pa_eval.py:104-124 upstream) for a batch, with the aligned set kept:
+    pred, gt (B,P,3) device tensors -> aligned (B,P,3) fp32 -- the points whose mean distance to ``gt`` ``PAEval`` reports (one
+    solve behind both).  ``return_transform``: also (B,13) fp64 = c, R (row-major), t with aligned = c R p + t.  One launch,
+    one wave per sample; no CPU fallback."""
+    from . import hip
+    if not pred.is_cuda:
+        raise RuntimeError("procrustes_align runs on the MI355X HIP path only (no CPU fallback)")
+    p, g = _dev32(pred, pred.device), _dev32(gt, pred.device)
+    if p.dim() != 3 or p.shape[2] != 3 or p.shape != g.shape or p.shape[1] < 3:
+        raise ValueError(f"pred and gt must both be (B,P,3) with P >= 3, got {tuple(p.shape)} and {tuple(g.shape)}")
+    out = torch.empty_like(p)
+    tr = torch.empty(p.shape[0], 13, dtype=torch.float64, device=p.device) if return_transform else None
+    with torch.cuda.device(p.device):
+        hip.check(hip.lib().poem_pa_align(hip.ptr(p), hip.ptr(g), hip.ptr(out), None if tr is None else tr.data_ptr(), p.shape[0],
+                                          p.shape[1], hip.stream()), "poem_pa_align")
+    return (out, tr) if return_transform else out
+
+
+def _nn_call(a, b, thresholds, want_dist, want_reduce, workspace=None):
+    """poem_nn_distance on device tensors a (B,na,3), b (B,nb,3): (d_ab, d_ba, counts (B,2,T) int32, sums (B,2) fp64, workspace)"""
+    import ctypes
+    from . import hip
+    if not a.is_cuda:
+        raise RuntimeError("nearest-neighbour distances run on the MI355X HIP path only (no CPU fallback)")
+    a, b = _dev32(a, a.device), _dev32(b, a.device)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[2] != 3 or b.shape[2] != 3 or a.shape[0] != b.shape[0] or 0 in a.shape or 0 in b.shape:
+        raise ValueError(f"a and b must be (B,na,3) and (B,nb,3), got {tuple(a.shape)} and {tuple(b.shape)}")
+    B, na, nb, T = a.shape[0], a.shape[1], b.shape[1], len(thresholds)
+    d_ab = torch.empty(B, na, dtype=torch.float32, device=a.device) if want_dist else None
+    d_ba = torch.empty(B, nb, dtype=torch.float32, device=a.device) if want_dist else None
+    counts = sums = None
+    need = 0
+    if want_reduce:
+        counts = torch.empty(B, 2, T, dtype=torch.int32, device=a.device) if T else None
+        sums = torch.empty(B, 2, dtype=torch.float64, device=a.device)
+        need = hip.lib().poem_nn_distance_workspace_bytes(B, na, nb, T)
+        if need == 0:
+            raise RuntimeError(f"poem_nn_distance does not take batch {B}, na {na}, nb {nb}, {T} thresholds")
+        if workspace is None or workspace.numel() < need or workspace.device != a.device:
+            workspace = torch.empty(need, dtype=torch.uint8, device=a.device)
+    thr = (ctypes.c_double * max(T, 1))(*[float(t) for t in thresholds])
+    with torch.cuda.device(a.device):
+        hip.check(hip.lib().poem_nn_distance(hip.ptr(a), na, hip.ptr(b), nb, hip.ptr(d_ab), hip.ptr(d_ba), thr if T else None, T,
+                                             None if counts is None else counts.data_ptr(), None if sums is None else sums.data_ptr(),
+                                             None if workspace is None else workspace.data_ptr(), need, B, hip.stream()),
+                  "poem_nn_distance")
+    return d_ab, d_ba, counts, sums, workspace
+
+
+def nearest_distances(a, b):
+    """a (B,na,3), b (B,nb,3) device tensors -> (d_ab (B,na), d_ba (B,nb)) fp32: the distance of every point of ``a`` to its nearest
+    point of ``b`` and the other way round -- the nearest-neighbour loop of the FreiHAND / HO3D evaluation scripts, brute force
+    in one launch.  A point with a NaN coordinate is nearest to nothing and nothing is nearest to it (include/poem_hip.h)."""
+    return _nn_call(a, b, (), True, False)[:2]
+
+
+class MeshFScore:
+    """Mesh F-scores of the FreiHAND / HO3D protocols, accumulated on the device (the protocol scripts loop over samples on the host
+    through open3d; the reference tree has no code of them).  Per sample: d_p = distance of every predicted vertex to its nearest
+    ground-truth vertex, d_g the other way; precision = #{d_p < t} / Np, recall = #{d_g < t} / Ng (strict ``<``, as the
+    scripts compare), F = 2 P R / (P + R), 0 where P + R = 0; the score is the mean of the per-sample F.  ``aligned``: the same
+    on ``procrustes_align(pred, gt)`` as well (keys ``PA_...``).  The search and the alignment are kernels; P / R / F come from
+    the integer counts in fp64.  No CPU fallback."""
+
+    def __init__(self, thresholds=(0.005, 0.015), aligned=True, device="cuda"):
+        self.thresholds = tuple(float(t) for t in thresholds)
+        if not 1 <= len(self.thresholds) <= 8 or any(not (t >= 0) for t in self.thresholds) or \
+                any(b <= a for a, b in zip(self.thresholds, self.thresholds[1:])):
+            raise ValueError(f"thresholds must be 1..8 ascending non-negative lengths in metres, got {thresholds}")
+        self.modes = ("", "PA_") if aligned else ("",)
+        self.device = torch.device(device)
+        M, T = len(self.modes), len(self.thresholds)
+        # this rank's sums: per (mode, threshold) F, P, R; per mode the mean d_p and mean d_g; the sample count
+        self.acc = torch.zeros(M * T * 3 + M * 2 + 1, dtype=torch.float64, device=self.device)
+        self._global = None
+        self._ws = None          # the search's workspace, grown as needed
+        self._n = None           # ((Np, Ng), their device tensor)
+        self.count = 0
+
+    def reset(self):
+        self.acc.zero_()
+        self._global = None
+        self.count = 0
+
+    def feed(self, pred_verts, gt_verts, **kwargs):
+        """pred_verts (B,Np,3), gt_verts (B,Ng,3) -> per-sample F (B, modes, T) fp64 on the device.  Launches and device
+        arithmetic only: nothing is copied to the host."""
+        pred, gt = _dev32(pred_verts, self.device), _dev32(gt_verts, self.device)
+        if not pred.is_cuda:
+            raise RuntimeError("MeshFScore runs on the MI355X HIP path only (no CPU fallback)")
+        if len(self.modes) > 1 and pred.shape != gt.shape:
+            raise ValueError("the aligned scores need vertex correspondence: pred and gt of one shape")
+        M, T, B = len(self.modes), len(self.thresholds), pred.shape[0]
+        # one search for every mode: the modes' sets stacked along the batch (a sample's bits do not depend on its batch)
+        src = torch.cat([pred, procrustes_align(pred, gt)]) if M > 1 else pred
+        tgt = torch.cat([gt, gt]) if M > 1 else gt
+        _, _, counts, sums, self._ws = _nn_call(src, tgt, self.thresholds, False, True, self._ws)
+        # (the point counts as a device tensor, filled on the device: a true division, and no copy in either direction)
+        key = (src.shape[1], tgt.shape[1])
+        if self._n is None or self._n[0] != key:
+            self._n = (key, torch.cat([torch.full((1,), float(k), dtype=torch.float64, device=self.device) for k in key]))
+        n = self._n[1]
+        pr = counts.double().view(M, B, 2, T) / n[None, None, :, None]          # precision, recall
+        p, r = pr[:, :, 0], pr[:, :, 1]                                          # (M,B,T)
+        f = torch.where(p + r > 0, 2.0 * p * r / (p + r), torch.zeros_like(p))
+        self.acc[:M * T * 3] += torch.stack([f.sum(1), p.sum(1), r.sum(1)], 2).reshape(-1)       # (M,T,3)
+        self.acc[M * T * 3:-1] += (sums.view(M, B, 2) / n[None, None, :]).sum(1).reshape(-1)     # (M,2)
+        self.acc[-1] += B
+        self.count += B
+        self._global = None
+        return f.permute(1, 0, 2).contiguous()
+
+    def reduce(self):
+        """all-reduce(sum) of a copy: the rank-local sums stay what this rank fed (``PAEval.reduce``'s contract)."""
+        self._global = pdist.all_reduce_sum_(self.acc.clone())
+        return self
+
+    def get_measures(self, **kwargs):
+        a = (self.acc if self._global is None else self._global).tolist()
+        M, T = len(self.modes), len(self.thresholds)
+        n = max(a[-1], 1.0)
+        m = {}
+        for mi, mode in enumerate(self.modes):
+            for ti, thr in enumerate(self.thresholds):
+                f, p, r = a[(mi * T + ti) * 3:(mi * T + ti) * 3 + 3]
+                key = f"{thr * 1000:g}"
+                m[f"{mode}F@{key}"], m[f"{mode}precision@{key}"], m[f"{mode}recall@{key}"] = f / n, p / n, r / n
+            m[f"{mode}chamfer_pred2gt"], m[f"{mode}chamfer_gt2pred"] = a[M * T * 3 + mi * 2] / n, a[M * T * 3 + mi * 2 + 1] / n
+        return m
+
+    def get_result(self):
+        return self.get_measures()[f"F@{self.thresholds[0] * 1000:g}"]
+
+    def __str__(self):
+        m = self.get_measures()
+        return " | ".join(f"{mode}F@{t * 1000:g}: {m[f'{mode}F@{t * 1000:g}']:6.4f}" for mode in self.modes for t in self.thresholds)
+
+
+class _PAFeed:
+    """``feed`` of the PCK metrics on Procrustes-aligned predictions: ``procrustes_align`` first, then the unchanged accumulation."""
+
+    def feed(self, preds, targs, **kwargs):
+        pk_, tk_ = self._keys[self.eval_type]
+        p, t = self._get_predictions(preds, targs)
+        p, t = _dev32(p, self.device), _dev32(t, self.device)
+        if not p.is_cuda:
+            raise RuntimeError("PCK metrics run on the MI355X HIP path only (no CPU fallback)")
+        return super().feed({pk_: procrustes_align(p, t)}, {tk_: t}, **kwargs)
+
+
+class PAJoint3DPCK(_PAFeed, Joint3DPCK):
+    """``Joint3DPCK`` of the aligned joints: the PA-AUC column of the FreiHAND / HO3D protocols (VAL_MAX 0.05, STEPS 100 there)."""
+
+
+class PAVert3DPCK(_PAFeed, Vert3DPCK):
+    """``Vert3DPCK`` of the aligned vertices."""

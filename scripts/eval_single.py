@@ -3,7 +3,8 @@
 
 Same command line (``--cfg --dataset --view_min --view_max --model -g --reload -p --draw``; ``--draw`` renders on the device and
 needs the mesh topology: ``--faces FILE.npy``, panels under ``--draw-dir``; ``--losses --j-regressor FILE.npy`` with ``--shards`` adds the
-averages of upstream's loss terms to the result line) and the same YAML edits
+averages of upstream's loss terms to the result line; ``--benchmark-scores`` adds the FreiHAND / HO3D leaderboard numbers, mesh
+F@5 / F@15 and the aligned AUCs, as a ``"benchmark"`` block) and the same YAML edits
 (scripts/eval_single.py:63-86 upstream: dataset URL / epoch size / view range, the four size fields derived from the
 model category, PARAMETRIC_OUTPUT for medium_MANO), written back to ``--cfg`` exactly as upstream does.  What differs:
 
@@ -33,7 +34,7 @@ if ROOT not in sys.path:
 
 import poem_v2_amd as pk  # noqa: E402
 from poem_v2_amd import dist as pdist  # noqa: E402
-from poem_v2_amd.metrics import Joint3DPCK, MeanEPE, PAEval, Vert3DPCK  # noqa: E402
+from poem_v2_amd.metrics import Joint3DPCK, MeanEPE, MeshFScore, PAEval, PAJoint3DPCK, PAVert3DPCK, Vert3DPCK  # noqa: E402
 from poem_v2_amd.triangulation import triangulate_reference_joints  # noqa: E402
 
 # scripts/eval_single.py:5-36 upstream (urls kept for the record; the tars are not shipped)
@@ -139,10 +140,35 @@ def install_template(head, reload, template, mano_assets=None):
     return "synthetic(seed=1234)"
 
 
+class BenchmarkScores:
+    """``--benchmark-scores``: the numbers of the FreiHAND / HO3D leaderboards that upstream's evaluation leaves to the protocol
+    scripts -- mesh F-scores at 5 / 15 mm, raw and Procrustes-aligned, the AUC of the aligned joints / vertices over 0..50 mm in
+    100 steps, and the symmetric mean nearest-vertex distance -- accumulated on the device next to the other metrics."""
+    PCK = dict(VAL_MIN=0.0, VAL_MAX=0.05, STEPS=100)
+
+    def __init__(self, device):
+        self.f = MeshFScore(thresholds=(0.005, 0.015), aligned=True, device=device)
+        self.pck_j = PAJoint3DPCK(device=device, EVAL_TYPE="joints_3d", **self.PCK)
+        self.pck_v = PAVert3DPCK(device=device, EVAL_TYPE="verts_3d", **self.PCK)
+
+    def feed(self, pred_joints, gt_joints, pred_verts, gt_verts):
+        self.f.feed(pred_verts, gt_verts)
+        self.pck_j.feed({"pred_joints_3d": pred_joints}, {"master_joints_3d": gt_joints})
+        self.pck_v.feed({"pred_verts_3d": pred_verts}, {"master_verts_3d": gt_verts})
+
+    def result(self):
+        """The ``"benchmark"`` block, reduced over ranks like the other metrics (every rank calls it)."""
+        m = self.f.reduce().get_measures()
+        return {"F@5": m["F@5"], "F@15": m["F@15"], "PA_F@5": m["PA_F@5"], "PA_F@15": m["PA_F@15"],
+                "pa_auc_j": self.pck_j.reduce().get_measures()["auc_all"], "pa_auc_v": self.pck_v.reduce().get_measures()["auc_all"],
+                "chamfer_mm": 0.5 * (m["chamfer_pred2gt"] + m["chamfer_gt2pred"]) * 1e3}
+
+
 def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, batch_size=2, seed=0, verbose=True,
-             pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, mano_assets=None):
+             pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, mano_assets=None,
+             benchmark_scores=False):
     """``draw``: a ``DrawingHandCallback`` (rank 0, ``--draw --faces``) called with every batch.  This scope has no images: the panels
-    show the meshes and skeletons over mid-grey views."""
+    show the meshes and skeletons over mid-grey views.  ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``)."""
     rank, _, world = pdist.env_world()
     if dlt_confidence != "off" and not pyramid:
         raise SystemExit("--dlt-confidence reads the heat maps' peaks: it needs --pyramid or --shards (this scope starts "
@@ -180,6 +206,7 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
     pa = PAEval(None, mesh_score=True, device=device)                       # lib/models/POEM.py:147 upstream
     pck = dict(VAL_MIN=0.0, VAL_MAX=0.02, STEPS=20)                         # AUCCallback defaults, lib/utils/testing.py:31
     pck_j, pck_v = Joint3DPCK(device=device, EVAL_TYPE="joints_3d", **pck), Vert3DPCK(device=device, EVAL_TYPE="verts_3d", **pck)
+    bench_scores = BenchmarkScores(device) if benchmark_scores else None
     n_done, t0, t_draw = 0, None, 0.0
     with torch.no_grad():
         for it, s in enumerate(range(lo, hi, batch_size)):
@@ -222,6 +249,8 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
             pa.feed(preds[-1, :, :21], gt[:, :21], preds[-1, :, 21:], gt[:, 21:])
             pck_j.feed({"pred_joints_3d": preds[-1, :, :21]}, {"master_joints_3d": gt[:, :21]})
             pck_v.feed({"pred_verts_3d": preds[-1, :, 21:]}, {"master_verts_3d": gt[:, 21:]})
+            if bench_scores is not None:
+                bench_scores.feed(preds[-1, :, :21], gt[:, :21], preds[-1, :, 21:], gt[:, 21:])
             if draw is not None:                           # rendering, the copy and the PNG files stay out of samples/s
                 torch.cuda.synchronize(device)
                 t_d = time.perf_counter()
@@ -247,6 +276,8 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
            "PA_MPVPE_mm": pam["pa_mpvpe"] * 1e3, "auc_j": pck_j.get_measures()["auc_all"], "auc_v": pck_v.get_measures()["auc_all"],
            "samples_per_s_rank0": (n_done / dt) if dt > 0 and n_done else None, "world_size": world,
            "template_source": template_source}
+    if bench_scores is not None:
+        res["benchmark"] = bench_scores.result()
     return res
 
 
@@ -255,7 +286,7 @@ BACKBONE_TYPES = {"hrnet": "HRNet", "resnet18": "ResNet18", "resnet34": "ResNet3
 
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
                     n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
-                    mano_assets=None, backbone_engine="torch", backbone="hrnet"):
+                    mano_assets=None, backbone_engine="torch", backbone="hrnet", benchmark_scores=False):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -265,6 +296,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     ``backbone``: "hrnet" | "resnet18" | "resnet34" | "resnet50" sets MODEL.BACKBONE.TYPE and MODEL.HEAD.IN_CHANNELS (160 / 128 / 512).
     ``losses``: MANO's (16,778) joint regressor (``--losses --j-regressor``): every batch's loss terms (upstream's ``compute_loss``,
     value only) feed the model's ``loss_metric`` on the device and the result gains their batch-size-weighted averages.
+    ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``), as ``evaluate`` does.
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
     shards of the same record layout are written there first."""
     rank, _, world = pdist.env_world()
@@ -315,6 +347,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     if model.ptEmb_head.parametric_output and not mano_assets:
         raise SystemExit("medium_MANO needs a MANO layer (licence-gated assets): pass --mano-assets FILE.npz")
     mpvpe, mpjpe = MeanEPE("verts", device=device), MeanEPE("joints", device=device)
+    bench_scores = BenchmarkScores(device) if benchmark_scores else None
     n, t0, frames, steps, t_draw = 0, None, [], [0], [0.0]
 
     def run(frames):
@@ -326,6 +359,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         gv = batch["master_verts_3d"].reshape(-1, 778, 3).to(device)
         mpjpe.feed(preds["pred_joints_3d"], gj)
         mpvpe.feed(preds["pred_verts_3d"], gv)
+        if bench_scores is not None:
+            bench_scores.feed(preds["pred_joints_3d"], gj, preds["pred_verts_3d"], gv)
         if losses is not None:                             # one launch + finalize, sums stay on the device (POEM.py:476,483 upstream)
             model.loss_metric.feed(model.compute_loss(preds, batch)[1], len(frames))
         if draw is not None:                               # kept out of samples/s, as in evaluate()
@@ -359,6 +394,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
            "template_source": template_source}
     if losses is not None:
         res["losses"] = model.loss_metric.reduce().get_measures()
+    if bench_scores is not None:
+        res["benchmark"] = bench_scores.result()
     return res
 
 
@@ -409,11 +446,13 @@ def main(args):
                               dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw,
                               losses=j_regressor, mano_assets=mano_assets,
                               backbone_engine=getattr(args, "backbone_engine", "torch"),
-                              backbone=getattr(args, "backbone", "hrnet"))
+                              backbone=getattr(args, "backbone", "hrnet"),
+                              benchmark_scores=getattr(args, "benchmark_scores", False))
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
-                       dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw, mano_assets=mano_assets)
+                       dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw, mano_assets=mano_assets,
+                       benchmark_scores=getattr(args, "benchmark_scores", False))
     if rank == 0:
         exp_id = f"{args.dataset}_view_{view_range[0]}_{view_range[1]}_{args.model}"
         if args.model == "huge":
@@ -478,6 +517,10 @@ def build_cli():
     parser.add_argument("--backbone", choices=tuple(BACKBONE_TYPES), default=argparse.SUPPRESS,
                         help="with --shards: the image backbone (default hrnet); sets MODEL.BACKBONE.TYPE and MODEL.HEAD.IN_CHANNELS "
                              "(160 / 128 / 512).")
+    parser.add_argument("--benchmark-scores", action="store_true", default=argparse.SUPPRESS,
+                        help="add a \"benchmark\" block to the result line: the FreiHAND / HO3D leaderboard numbers -- mesh F@5 / F@15, raw "
+                             "and Procrustes-aligned (PA_), the AUC of the aligned joints / vertices over 0..50 mm (pa_auc_j / pa_auc_v) "
+                             "and the symmetric mean nearest-vertex distance (chamfer_mm) -- computed on the device.")
     return parser
 
 
