@@ -142,6 +142,17 @@ def test_rot6d_kernel_is_pinned_to_rodrigues():
     assert float((aa - ref)[~near_pi].abs().max()) < 2e-5
 
 
+def _assert_under_the_lbs_bar(v, j, vo, jo, pose, betas, c):
+    """tests/test_tail_forms.py's bar in place of a flat 2e-6 m, which measured three to seven times looser: per sample, joints and
+    vertices separately, |HIP - fp64| <= 4 |fp32 oracle - fp64| + 2^-23 max|fp64|"""
+    import tail_forms_util as tf
+    v32, j32 = mo.mano_lbs(_assets(), pose, betas, center_idx=c, dtype=torch.float32)
+    for name, got, r64, r32 in (("verts", v, vo, v32), ("joints", j, jo, j32)):
+        err = (got - r64).abs().flatten(1).amax(1)
+        bar, _ = tf.lbs_bar(r64, r32)
+        assert float(bar.max()) < 2e-6 and bool((err <= bar).all()), (c, name, float((err / bar).max()))
+
+
 @pytest.mark.gpu
 def test_mano_kernel_properties_and_oracle():
     import poem_v2_amd as pk
@@ -155,7 +166,7 @@ def test_mano_kernel_properties_and_oracle():
     pose, betas = 0.6 * torch.randn(32, 48, generator=g), torch.randn(32, 10, generator=g)
     v, j = run(pose, betas, 9)
     vo, jo = mo.mano_lbs(_assets(), pose, betas, center_idx=9)
-    assert float((v - vo).abs().max()) < 2e-6 and float((j - jo).abs().max()) < 2e-6      # metres
+    _assert_under_the_lbs_bar(v, j, vo, jo, pose, betas, 9)
     one = run(pose[7:8], betas[7:8], 9)
     assert torch.equal(one[0][0], v[7]) and torch.equal(one[1][0], j[7])                      # batch independence
     mpvpe = float(torch.linalg.norm(v - vo, dim=-1).mean())
@@ -167,7 +178,7 @@ def test_mano_kernel_properties_and_oracle():
         assert float(jc[:, c].abs().max()) == 0.0, c                                          # the centre joint is exactly 0
         assert float((vc - (vu - ju[:, c:c + 1])).abs().max()) < 2e-7 and float((jc - (ju - ju[:, c:c + 1])).abs().max()) < 2e-7, c
         voc, joc = mo.mano_lbs(_assets(), pose, betas, center_idx=c)
-        assert float((vc - voc).abs().max()) < 2e-6 and float((jc - joc).abs().max()) < 2e-6, c
+        _assert_under_the_lbs_bar(vc, jc, voc, joc, pose, betas, c)
     layer = pk.ManoLayer(_assets(), device=DEV)
     t = layer.zero_pose_template()
     assert t.shape == (799, 3) and float(t[9].abs().max()) == 0.0

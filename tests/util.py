@@ -234,3 +234,12 @@ class SampleGroupArgs(ctypes.Structure):
 class MergeTailArgs(ctypes.Structure):
     _fields_ = [("h2", _P), ("q1", _P), ("offs", _P), ("w0", _P), ("b0", _P), ("w1", _P), ("b1", _P), ("out", _P),
                 ("B", _I), ("S", _I), ("h2_tiled", _I), ("group_min_views", _I), ("views_dev", _P), ("views", _I)]
+
+
+# ---- ctypes mirror of ViewLayoutArgs (poem-v2_amd/csrc/merge.h): what tests/test_tail_forms.py hands poem_launch_view_layout by
+# pointer -- the batch's view offsets travel as 16-bit values inside the argument block itself.
+LAYOUT_MAX_BATCH = 1663      # POEM_LAYOUT_MAX_BATCH
+
+
+class ViewLayoutArgs(ctypes.Structure):
+    _fields_ = [("offs", _P), ("view_sample", _P), ("pe_index", _P), ("B", _I), ("off16", ctypes.c_ushort * (LAYOUT_MAX_BATCH + 1))]
