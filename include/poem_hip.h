@@ -357,7 +357,9 @@ int poem_cross_attention(const float* q, const float* k, const float* v, float* 
  * per-sample loop of lib/models/POEM.py:284-299: uv (BN,J,2) pixels, cam_intr (BN,3,3), cam_mat (BN,4,4),
  * view_offsets (B+1) DEVICE int32 prefix sums of views per sample -> out_xyz (B,J,3) in the master frame.
  * invert=1: cam_mat is the batch's cam_extr (camera->master) and is inverted here (POEM.py:286);
- * invert=0: cam_mat is already master->camera (the `Extrs` argument of the reference function). */
+ * invert=0: cam_mat is already master->camera (the `Extrs` argument of the reference function).
+ * batch * njoints <= INT32_MAX (the kernels index (sample, joint) in 32 bits): POEM_E_UNSUPPORTED beyond it, here and
+ * in poem_dlt_confidence; nothing is launched. */
 int poem_triangulate_dlt(const float* uv, const float* cam_intr, const float* cam_mat, const int32_t* view_offsets,
                          int batch, int njoints, int invert, float* out_xyz, void* stream);
 /* Heat-map read-out in front of the triangulation (tail of heatmap_stage, lib/models/POEM.py:213-222, with
@@ -379,7 +381,8 @@ int poem_heatmap_uv_conf(const float* heatmaps, float* uv, float* conf, int view
  *   threshold <= 64 (NaN refused).  A joint left with fewer than two cameras has no triangulation; sel_count tells.
  * mode POEM_DLT_WEIGHTED: both rows of view n are scaled by conf[n][j]; no view is dropped; threshold is ignored.
  * conf == 1 everywhere (weighted), or threshold 0 with positive conf, reproduces poem_triangulate_dlt bit for bit.
- * njoints <= 4096.  Stream-ordered like every other call: no host synchronisation, no copy. */
+ * njoints <= 4096; batch * njoints <= INT32_MAX (POEM_E_UNSUPPORTED beyond it).  Stream-ordered like every other call:
+ * no host synchronisation, no copy. */
 #define POEM_DLT_THRESHOLD 1
 #define POEM_DLT_WEIGHTED 2
 int poem_dlt_confidence(const float* uv, const float* conf, const float* cam_intr, const float* cam_mat,
@@ -601,7 +604,9 @@ int poem_attach_mano(poem_handle_t h, const void* table, int center_idx);
  * of each image; src_hw (views,2) = (height, width); m_inv (views,6) fp64 = the INVERSE (destination -> source) 2x3 map,
  * i.e. what cv::warpAffine derives from the matrix it is given; gain (views,3) fp64 per-channel colour gains or NULL.
  * Outputs (either may be NULL, not both): out_f32 (views,3,out_h,out_w) = p / 255 - 0.5; out_u8 (views,out_h,out_w,3).
- * Arithmetic is OpenCV's 8-bit fixed-point bilinear path (1/32-pixel coordinates, 15-bit weights): integer, bit-exact. */
+ * Arithmetic is OpenCV's 8-bit fixed-point bilinear path (1/32-pixel coordinates, 15-bit weights): integer, bit-exact.
+ * Any out_u8 base and any 4-byte aligned out_f32 base will do: the wide stores are taken only when out_w % 4 == 0 and the bases
+ * sit on 4 (out_u8) and 16 (out_f32) bytes, the scalar ones otherwise.  POEM_E_UNSUPPORTED: views > 65535 or out_h > 262140. */
 int poem_warp_affine(const uint8_t* src, const int64_t* src_offsets, const int32_t* src_hw, const double* m_inv,
                      const double* gain, float* out_f32, uint8_t* out_u8, int views, int out_h, int out_w, void* stream);
 /* Operator-level entry points of the opt-in split-precision vector attention (see poem_set_precision).

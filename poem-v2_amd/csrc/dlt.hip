@@ -5,8 +5,13 @@
 //   A   = [u_n M_n[2] - M_n[0] ; v_n M_n[2] - M_n[1]]_n          (2 N_i x 4)
 //   x   = right singular vector of A for the smallest singular value;  X = x[:3] / (x[3] + 1e-7)
 // The reference calls torch.linalg.svd on every (2N x 4) matrix; here the 4x4 normal matrix A^T A is accumulated in
-// fp64 and its smallest eigenvector found with cyclic Jacobi rotations in fp64 (same subspace; measured closer to the
-// fp64 SVD than the reference's fp32 SVD is).  dlt_kernel: one thread per (sample, joint), the whole stage is ~700 threads.
+// fp64 and its smallest eigenvector found with cyclic Jacobi rotations in fp64 (same subspace).  Accuracy, measured on the
+// conditioning ladder of tests/test_dlt_forms.py against the fp64 SVD of the same fp32 rows: for sigma1/sigma3 up to 1e4 every
+// joint is within one fp32 rounding of the fp64 answer and closer to it than an fp32 SVD of those rows is; at 1e5 (a 0.03 mm
+// baseline at 0.6 m) that no longer holds for every joint -- forming A^T A costs cond(A)^2 2^-53.  Physical rigs sit below 1e3.
+// The sign of x is fixed to x[3] >= 0 (LAPACK returns either; with the + 1e-7 the two differ by 2e-7 |X| / x[3]).  A NaN or an
+// infinite uv makes its joint NaN, a NaN camera its whole sample; nothing else is touched.
+// dlt_kernel: one thread per (sample, joint), the whole stage is ~700 threads.
 #include "common.h"
 
 #define DLT_MODE_THRESHOLD 1
@@ -62,7 +67,8 @@ __device__ __forceinline__ int dlt_solve(const float* __restrict__ uv, const flo
   for (int sweep = 0; sweep < 12; ++sweep) {
     double off = 0.0, diag = 0.0;
     for (int r = 0; r < 4; ++r) { diag += G[r][r] * G[r][r]; for (int c = r + 1; c < 4; ++c) off += G[r][c] * G[r][c]; }
-    if (off <= 1e-40 * diag) break;
+    if (off <= 1e-40 * diag && diag < HUGE_VAL) break;                             // (inf <= inf: an infinite G, from an infinite uv, is
+                                                                                   //  not converged; it rotates on into NaN, as a NaN does)
     for (int p = 0; p < 3; ++p)
       for (int q = p + 1; q < 4; ++q) {
         if (G[p][q] == 0.0) continue;
@@ -88,16 +94,16 @@ __device__ __forceinline__ int dlt_solve(const float* __restrict__ uv, const flo
 __global__ __launch_bounds__(64) void dlt_kernel(const float* __restrict__ uv, const float* __restrict__ intr,
                                                  const float* __restrict__ mat, const int* __restrict__ offs,
                                                  float* __restrict__ out, int B, int J, int invert) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= B * J) return;
-  const int b = t / J, j = t % J;
+  const unsigned t = blockIdx.x * blockDim.x + threadIdx.x;                      // B * J fits an int (poem_triangulate_dlt): the last
+  if (t >= (unsigned)(B * J)) return;                                            // block's spare threads stay below 2^32
+  const int b = (int)(t / (unsigned)J), j = (int)(t % (unsigned)J);
   dlt_solve<false>(uv, nullptr, intr, mat, offs[b], offs[b + 1], J, j, invert, 0, 0.0, out + (size_t)t * 3);
 }
 
 extern "C" hipError_t poem_launch_dlt(const float* uv, const float* intr, const float* mat, const int* offs, float* out,
                                       int B, int J, int invert, hipStream_t s) {
-  const int total = B * J;
-  hipLaunchKernelGGL(dlt_kernel, dim3((total + 63) / 64), dim3(64), 0, s, uv, intr, mat, offs, out, B, J, invert);
+  const unsigned total = (unsigned)B * (unsigned)J;                              // <= INT_MAX: the entry point refuses more
+  hipLaunchKernelGGL(dlt_kernel, dim3((total + 63u) / 64u), dim3(64), 0, s, uv, intr, mat, offs, out, B, J, invert);
   return hipGetLastError();
 }
 

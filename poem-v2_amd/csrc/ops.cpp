@@ -1,6 +1,7 @@
 // Operator-level entry points of libpoem_hip.so (include/poem_hip.h names the reference call each one replaces): argument
 // checks around the launchers of launchers.h.  Stream-ordered, no allocation.
 #include <cmath>
+#include <cstdint>
 #include <cstring>
 #include "engine.h"
 
@@ -236,6 +237,7 @@ int poem_triangulate_dlt(const float* uv, const float* cam_intr, const float* ca
                          int batch, int njoints, int invert, float* out_xyz, void* stream) {
   if (!uv || !cam_intr || !cam_mat || !view_offsets || !out_xyz || batch <= 0 || njoints <= 0 || (invert & ~1))
     return POEM_E_ARG;
+  if ((int64_t)batch * njoints > INT32_MAX) return POEM_E_UNSUPPORTED;    // the launcher and the kernel index (sample, joint) in int
   HIPCHK(poem_launch_dlt(uv, cam_intr, cam_mat, view_offsets, out_xyz, batch, njoints, invert, (hipStream_t)stream));
   return POEM_OK;
 }
@@ -262,6 +264,7 @@ int poem_dlt_confidence(const float* uv, const float* conf, const float* cam_int
     return POEM_E_ARG;
   // the lowering loop runs (threshold / 0.05) times at most; an infinite or absurd threshold would never get there
   if (mode == POEM_DLT_THRESHOLD && !(threshold <= 64.0)) return POEM_E_ARG;
+  if ((int64_t)batch * njoints > INT32_MAX) return POEM_E_UNSUPPORTED;    // one limit for both triangulation entry points
   HIPCHK(poem_launch_dlt_confidence(uv, conf, cam_intr, cam_mat, view_offsets, out_xyz, sel_count, batch, njoints, invert, mode,
                                     threshold, (hipStream_t)stream));
   return POEM_OK;

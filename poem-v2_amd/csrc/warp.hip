@@ -54,7 +54,7 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const unsigned char* _
                                                           const long long* __restrict__ src_off,
                                                           const int* __restrict__ src_hw, const double* __restrict__ minv,
                                                           const double* __restrict__ gain, float* __restrict__ out_f32,
-                                                          unsigned char* __restrict__ out_u8, int OH, int OW) {
+                                                          unsigned char* __restrict__ out_u8, int OH, int OW, int vec) {
   const int x4 = (blockIdx.x * 64 + threadIdx.x) * 4, y = blockIdx.y * 4 + threadIdx.y, v = blockIdx.z;
   if (x4 >= OW || y >= OH) return;
   const double* M = minv + (size_t)v * 6;
@@ -73,7 +73,7 @@ __global__ __launch_bounds__(256) void warp_affine_kernel(const unsigned char* _
     else p[i][0] = p[i][1] = p[i][2] = 0;
   }
   const size_t plane = (size_t)OH * OW;
-  if (n == 4 && (OW & 3) == 0) {
+  if (vec) {                                        // OW % 4 == 0 (so n == 4) and both bases aligned: the launcher's rule
     if (out_u8) {                                   // 12 bytes, 4-byte aligned ((v*OH + y)*OW + x4) * 3 with OW, x4 % 4 == 0
       unsigned int* o = reinterpret_cast<unsigned int*>(out_u8 + (((size_t)v * OH + y) * OW + x4) * 3);
       o[0] = (unsigned)p[0][0] | ((unsigned)p[0][1] << 8) | ((unsigned)p[0][2] << 16) | ((unsigned)p[1][0] << 24);
@@ -110,6 +110,9 @@ extern "C" hipError_t poem_launch_warp_affine(const unsigned char* src, const lo
                                    const double* minv, const double* gain, float* out_f32, unsigned char* out_u8, int views,
                                    int OH, int OW, hipStream_t s) {
   dim3 grid((OW + 255) / 256, (OH + 3) / 4, views);
-  warp_affine_kernel<<<grid, dim3(64, 4), 0, s>>>(src, src_off, src_hw, minv, gain, out_f32, out_u8, OH, OW);
+  // dword / float4 stores only where they are aligned: a width that is a multiple of 4 and bases on 4 (u8) and 16 (f32) bytes, as
+  // poem_launch_render_raster's `packed` looks at its rgb base; anything else takes the scalar stores
+  const int vec = (OW & 3) == 0 && ((uintptr_t)out_u8 & 3) == 0 && ((uintptr_t)out_f32 & 15) == 0;
+  warp_affine_kernel<<<grid, dim3(64, 4), 0, s>>>(src, src_off, src_hw, minv, gain, out_f32, out_u8, OH, OW, vec);
   return hipGetLastError();
 }
