@@ -40,6 +40,8 @@
  *   poem_dlt_confidence /     triangulate_dlt (lib/utils/triangulation.py:111-148): the same stage with views selected by a
  *   poem_heatmap_uv_conf      confidence threshold that drops until two are left, or weighted by confidence; the confidence
  *                             is the heat map's peak, read out next to the expectation
+ *   poem_dlt_robust           (no upstream counterpart) the same stage with views that disagree with the geometry of the others
+ *                             left out: exhaustive two-view hypotheses, inlier count, refit, optional Gauss-Newton refinement
  *   poem_conv3x3 /            ConvBlock (Conv2d 3x3 + BatchNorm(eval) + ReLU, lib/models/bricks/conv.py:4-45) and the glue
  *   poem_upsample2_concat_pad around it in PtEmbedMultiviewStereoV2.feat_decode / uv_decode (lib/models/POEM.py:167-211:
  *   poem_pool_conv1x1_sigmoid F.interpolate x2 + torch.cat, max_pool2d + uv_out + sigmoid); poem_heatmap_uv is the read-out of
@@ -388,6 +390,26 @@ int poem_heatmap_uv_conf(const float* heatmaps, float* uv, float* conf, int view
 int poem_dlt_confidence(const float* uv, const float* conf, const float* cam_intr, const float* cam_mat,
                         const int32_t* view_offsets, float* out_xyz, int32_t* sel_count, int batch, int njoints, int invert,
                         int mode, double threshold, void* stream);
+/* Outlier-robust ragged DLT.  Upstream has NO counterpart (lib/utils/triangulation.py stops at triangulate_dlt, which trusts every
+ * view's 2-D joint); the definition is the one below, restated in fp64 in tests/dlt_robust_util.py.  Arguments as
+ * poem_dlt_confidence without conf / mode / threshold.  Per (sample, joint), deterministic and exhaustive (no random sampling):
+ *   every pair of the sample's views gives a two-view solve (poem_triangulate_dlt's arithmetic); view v is an inlier of it iff
+ *   its reprojection error is < inlier_px pixels AND its depth is > 0 (both strict: a NaN is never an inlier); the pair with the
+ *   most inliers wins, ties by the smaller summed squared error of the inliers, then by the smaller a * N + c.  With >= 2
+ *   inliers the joint is solved again over the inlier set (the bits poem_triangulate_dlt gives those views alone); otherwise,
+ *   and for every joint of a sample with a camera that is not finite, over all views with an empty inlier set (the bits of
+ *   poem_triangulate_dlt, NaN behaviour included).  Then `refine` (0..16) Gauss-Newton steps on the summed squared reprojection
+ *   error of the views solved over, fp64, each kept only if the error gets strictly smaller.
+ * Limit of the method: with 3 views and one outlier every pair explains itself (all counts tie at 2) and the residual
+ * tie-break does not identify the outlier; an outlier is found where at least three clean views remain.
+ * Optional outputs (each may be NULL): inlier (BN,J) uint8; inlier_count (B,J) int32 (0 after the fallback); reproj_px (BN,J)
+ * fp32 = the final joint's reprojection error in every view in pixels, inlier or not, NaN where it is not finite.
+ * inlier_px > 0 (NaN refused; +inf = every view in front of the point), njoints <= 4096, batch * njoints <= INT32_MAX, else
+ * POEM_E_ARG.  Every sample needs 2..64 views: the caller checks that (nothing on the device is read by the host); a sample
+ * outside it gets NaN joints and residuals and count 0.  Stream-ordered, no host synchronisation, no workspace. */
+int poem_dlt_robust(const float* uv, const float* cam_intr, const float* cam_mat, const int32_t* view_offsets, float* out_xyz,
+                    uint8_t* inlier, int32_t* inlier_count, float* reproj_px, int batch, int njoints, int invert,
+                    double inlier_px, int refine, void* stream);
 /* Convolutional glue between the backbone's multi-level features and the head -- replaces
  * PtEmbedMultiviewStereoV2.feat_decode / uv_decode (lib/models/POEM.py:167-211, HRNet branch) built from
  * lib/models/bricks/conv.py ConvBlocks.  The Python mirror (poem_v2_amd/decode.py) chains them exactly as the

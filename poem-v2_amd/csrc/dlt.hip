@@ -11,56 +11,49 @@
 // baseline at 0.6 m) that no longer holds for every joint -- forming A^T A costs cond(A)^2 2^-53.  Physical rigs sit below 1e3.
 // The sign of x is fixed to x[3] >= 0 (LAPACK returns either; with the + 1e-7 the two differ by 2e-7 |X| / x[3]).  A NaN or an
 // infinite uv makes its joint NaN, a NaN camera its whole sample; nothing else is touched.
-// dlt_kernel: one thread per (sample, joint), the whole stage is ~700 threads.
+// dlt_kernel: one thread per (sample, joint), the whole stage is ~700 threads.  dlt_conf_kernel: the same solve with views chosen
+// or weighted by confidence.  dlt_robust_kernel: the same solve with the views that disagree with the others' geometry left out.
 #include "common.h"
 
 #define DLT_MODE_THRESHOLD 1
 #define DLT_MODE_WEIGHTED 2
 
-// Joint j of a sample over its views v0..v1 -> o[0..2]; returns the number of views that took part.  CONF = false is the plain
-// solve (conf, mode and thr are not read).  CONF = true, the confidence-aware form (below): a view takes part when its
-// confidence is above thr (mode 1), or both its rows are scaled by its confidence (mode 2).  Everything else is one
-// arithmetic -- M and the rows in fp32, normal matrix and Jacobi in fp64, the sign, the +1e-7 of :43 -- so that confidence 1
-// everywhere (mode 2) or a threshold of 0 with positive confidences (mode 1) gives the plain solve's bits.
-template <bool CONF>
-__device__ __forceinline__ int dlt_solve(const float* __restrict__ uv, const float* __restrict__ conf,
-                                         const float* __restrict__ intr, const float* __restrict__ mat, int v0, int v1, int J,
-                                         int j, int invert, int mode, double thr, float* __restrict__ o) {
-  int used = 0;
-  double G[4][4] = {};
-  for (int v = v0; v < v1; ++v) {
-    double cf = 1.0;
-    if constexpr (CONF) {
-      cf = (double)conf[(size_t)v * J + j];
-      if (mode == DLT_MODE_THRESHOLD && !(cf > thr)) continue;                   // :135
-    }
-    ++used;
-    float T[3][4];
-    if (invert) {
-      double Ti[16];
-      invert4x4(mat + (size_t)v * 16, Ti);                                        // (common.h)
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = (float)Ti[r * 4 + c];
-    } else {
-      for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = mat[(size_t)v * 16 + r * 4 + c];
-    }
-    const float* K = intr + (size_t)v * 9;
-    float M[3][4];
-    for (int r = 0; r < 3; ++r)
-      for (int c = 0; c < 4; ++c) M[r][c] = fmaf(K[r * 3 + 2], T[2][c], fmaf(K[r * 3 + 1], T[1][c], K[r * 3] * T[0][c]));
-    const float u = uv[((size_t)v * J + j) * 2], w = uv[((size_t)v * J + j) * 2 + 1];
-    float a0[4], a1[4];
-    for (int c = 0; c < 4; ++c) { a0[c] = u * M[2][c] - M[0][c]; a1[c] = w * M[2][c] - M[1][c]; }
-    if constexpr (CONF) {
-      const double sc = mode == DLT_MODE_WEIGHTED ? cf : 1.0;
-      double d0[4], d1[4];
-      for (int c = 0; c < 4; ++c) { d0[c] = (double)a0[c] * sc; d1[c] = (double)a1[c] * sc; }
-      for (int r = 0; r < 4; ++r)
-        for (int c = r; c < 4; ++c) G[r][c] += d0[r] * d0[c] + d1[r] * d1[c];
-    } else {
-      for (int r = 0; r < 4; ++r)
-        for (int c = r; c < 4; ++c) G[r][c] += (double)a0[r] * (double)a0[c] + (double)a1[r] * (double)a1[c];
-    }
+// The solve in three pieces, shared by every kernel of this file so that all of them have one arithmetic (a view set solved by one
+// kernel has the bits another kernel gives it): dlt_view_matrix (M = K . T in fp32), dlt_add_view (the view's two fp32 rows into the
+// fp64 normal matrix) and dlt_null_vector (cyclic Jacobi, the sign, the +1e-7 of :43).
+__device__ __forceinline__ void dlt_view_matrix(const float* __restrict__ intr, const float* __restrict__ mat, int v, int invert,
+                                                float M[3][4]) {
+  float T[3][4];
+  if (invert) {
+    double Ti[16];
+    invert4x4(mat + (size_t)v * 16, Ti);                                          // (common.h)
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = (float)Ti[r * 4 + c];
+  } else {
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) T[r][c] = mat[(size_t)v * 16 + r * 4 + c];
   }
+  const float* K = intr + (size_t)v * 9;
+  for (int r = 0; r < 3; ++r)
+    for (int c = 0; c < 4; ++c) M[r][c] = fmaf(K[r * 3 + 2], T[2][c], fmaf(K[r * 3 + 1], T[1][c], K[r * 3] * T[0][c]));
+}
+
+// G (upper triangle) += the two rows of a view that saw the joint at (u, w).  SCALED: both rows times sc in fp64 (weighted mode).
+template <bool SCALED>
+__device__ __forceinline__ void dlt_add_view(const float M[3][4], float u, float w, double sc, double G[4][4]) {
+  float a0[4], a1[4];
+  for (int c = 0; c < 4; ++c) { a0[c] = u * M[2][c] - M[0][c]; a1[c] = w * M[2][c] - M[1][c]; }
+  if constexpr (SCALED) {
+    double d0[4], d1[4];
+    for (int c = 0; c < 4; ++c) { d0[c] = (double)a0[c] * sc; d1[c] = (double)a1[c] * sc; }
+    for (int r = 0; r < 4; ++r)
+      for (int c = r; c < 4; ++c) G[r][c] += d0[r] * d0[c] + d1[r] * d1[c];
+  } else {
+    for (int r = 0; r < 4; ++r)
+      for (int c = r; c < 4; ++c) G[r][c] += (double)a0[r] * (double)a0[c] + (double)a1[r] * (double)a1[c];
+  }
+}
+
+// Upper triangle of the normal matrix -> X = x[:3] / (x[3] + 1e-7) of its smallest eigenvector x, in fp64.
+__device__ __forceinline__ void dlt_null_vector(double G[4][4], double X[3]) {
   for (int r = 1; r < 4; ++r) for (int c = 0; c < r; ++c) G[r][c] = G[c][r];
   // cyclic Jacobi: G <- R^T G R, V <- V R
   double V[4][4] = {{1, 0, 0, 0}, {0, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 0, 1}};
@@ -81,13 +74,45 @@ __device__ __forceinline__ int dlt_solve(const float* __restrict__ uv, const flo
       }
   }
   int m = 0;
-  for (int k = 1; k < 4; ++k) if (G[k][k] < G[m][m]) m = k;
-  double x[4] = {V[0][m], V[1][m], V[2][m], V[3][m]};
+  double gm = G[0][0];
+  for (int k = 1; k < 4; ++k) if (G[k][k] < gm) { gm = G[k][k]; m = k; }
+  double x[4];                                                                     // column m of V by selects: V[k][m] with a run-time
+  for (int k = 0; k < 4; ++k) x[k] = m == 0 ? V[k][0] : m == 1 ? V[k][1] : m == 2 ? V[k][2] : V[k][3];   // m would put V in scratch
   if (x[3] < 0) { x[0] = -x[0]; x[1] = -x[1]; x[2] = -x[2]; x[3] = -x[3]; }        // the sign of a singular vector is free
   const double den = x[3] + 1e-7;                                                  // triangulation.py:43
-  o[0] = (float)(x[0] / den);
-  o[1] = (float)(x[1] / den);
-  o[2] = (float)(x[2] / den);
+  X[0] = x[0] / den;
+  X[1] = x[1] / den;
+  X[2] = x[2] / den;
+}
+
+// Joint j of a sample over its views v0..v1 -> o[0..2]; returns the number of views that took part.  CONF = false is the plain
+// solve (conf, mode and thr are not read).  CONF = true, the confidence-aware form (below): a view takes part when its
+// confidence is above thr (mode 1), or both its rows are scaled by its confidence (mode 2).  Everything else is one
+// arithmetic -- M and the rows in fp32, normal matrix and Jacobi in fp64, the sign, the +1e-7 of :43 -- so that confidence 1
+// everywhere (mode 2) or a threshold of 0 with positive confidences (mode 1) gives the plain solve's bits.
+template <bool CONF>
+__device__ __forceinline__ int dlt_solve(const float* __restrict__ uv, const float* __restrict__ conf,
+                                         const float* __restrict__ intr, const float* __restrict__ mat, int v0, int v1, int J,
+                                         int j, int invert, int mode, double thr, float* __restrict__ o) {
+  int used = 0;
+  double G[4][4] = {};
+  for (int v = v0; v < v1; ++v) {
+    double cf = 1.0;
+    if constexpr (CONF) {
+      cf = (double)conf[(size_t)v * J + j];
+      if (mode == DLT_MODE_THRESHOLD && !(cf > thr)) continue;                   // :135
+    }
+    ++used;
+    float M[3][4];
+    dlt_view_matrix(intr, mat, v, invert, M);
+    const float u = uv[((size_t)v * J + j) * 2], w = uv[((size_t)v * J + j) * 2 + 1];
+    dlt_add_view<CONF>(M, u, w, CONF && mode == DLT_MODE_WEIGHTED ? cf : 1.0, G);
+  }
+  double X[3];
+  dlt_null_vector(G, X);
+  o[0] = (float)X[0];
+  o[1] = (float)X[1];
+  o[2] = (float)X[2];
   return used;
 }
 
@@ -158,6 +183,189 @@ extern "C" hipError_t poem_launch_dlt_confidence(const float* uv, const float* c
   const size_t lds = mode == DLT_MODE_THRESHOLD ? (size_t)J * sizeof(double) : 0;
   hipLaunchKernelGGL(dlt_conf_kernel, dim3(B), dim3(64), lds, s, uv, conf, intr, mat, offs, out, sel_count, J, invert, mode,
                      threshold);
+  return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Outlier-robust form of the same solve (upstream has no counterpart: lib/utils/triangulation.py stops at triangulate_dlt).  A view
+// whose 2-D joint is confidently wrong -- a heat map that peaks on another finger, the held object, the other hand -- is found from
+// geometry alone.  Deterministic and exhaustive over minimal samples, no random sampling: per (sample, joint)
+//   1. every pair (a < c) of the sample's N views gives a two-view solve X (fp64);
+//   2. view v is an inlier of X iff |proj_v(X) - uv_v|^2 < px^2 AND depth_v(X) > 0 (both strict: a NaN is never an inlier); the
+//      pair's key is (-count, sum of the inliers' r^2 in view order, a N + c), the smallest key wins;
+//   3. with >= 2 inliers the joint is solved again over the inlier set (ascending, unweighted), else over all views with an
+//      empty inlier set (count 0) -- the plain solve, NaN behaviour included.  A camera that is not finite sends its whole sample
+//      down that second road: a NaN camera is a broken calibration and not an outlier, and it makes its sample NaN as it always has;
+//   4. `refine` Gauss-Newton steps on the inliers' (after the fallback: all views') summed r^2 in fp64, 3x3 normal equations,
+//      J = (M[:2,:3] - p M[2,:3]) / h[2]; a step is kept only while the cost gets strictly smaller.
+// One wave per (sample, joint), four per block; grid (B, ceil(J / 4)).  The block's first N threads form their view's M once
+// (dlt_view_matrix, the fp64 inverse included) into LDS, 12 floats per view.  The lanes of a wave stride over the N (N - 1) / 2
+// pairs (one pass up to N = 11), each keeps its best key and inlier mask, __shfl_xor reduces them (the key is a strict total
+// order, so every lane ends with the same winner whatever the lane order); refit and refinement run redundantly on all lanes
+// (no broadcast), then lane v writes view v's inlier flag and residual.  The inlier set is one 64-bit mask: N <= 64.  A sample
+// with fewer than 2 or more than 64 views is not solved: NaN joints and residuals, count 0 (the Python layer refuses it).
+#define DLT_ROBUST_MAX_VIEWS 64
+
+// r^2 of X in the view whose M is m[0..11]; *depth = h[2]
+__device__ __forceinline__ double dlt_reproj2(const float* __restrict__ m, const double X[3], float u, float w, double* depth) {
+  const double h0 = (double)m[0] * X[0] + (double)m[1] * X[1] + (double)m[2] * X[2] + (double)m[3];
+  const double h1 = (double)m[4] * X[0] + (double)m[5] * X[1] + (double)m[6] * X[2] + (double)m[7];
+  const double h2 = (double)m[8] * X[0] + (double)m[9] * X[1] + (double)m[10] * X[2] + (double)m[11];
+  const double du = h0 / h2 - (double)u, dv = h1 / h2 - (double)w;
+  *depth = h2;
+  return du * du + dv * dv;
+}
+
+// the solve over the views of `mask` (bit v = view v0 + v), ascending
+__device__ __forceinline__ void dlt_solve_mask(const float* __restrict__ Ms, const float* __restrict__ uvj, int N, int J,
+                                               unsigned long long mask, double X[3]) {
+  double G[4][4] = {};
+  for (int v = 0; v < N; ++v) {
+    if (!((mask >> v) & 1ull)) continue;
+    float M[3][4];
+    for (int r = 0; r < 3; ++r) for (int c = 0; c < 4; ++c) M[r][c] = Ms[v * 12 + r * 4 + c];
+    dlt_add_view<false>(M, uvj[(size_t)v * J * 2], uvj[(size_t)v * J * 2 + 1], 1.0, G);
+  }
+  dlt_null_vector(G, X);
+}
+
+// sum over the views of `mask` of r^2 at X
+__device__ __forceinline__ double dlt_mask_cost(const float* __restrict__ Ms, const float* __restrict__ uvj, int N, int J,
+                                                unsigned long long mask, const double X[3]) {
+  double cost = 0.0, depth;
+  for (int v = 0; v < N; ++v)
+    if ((mask >> v) & 1ull) cost += dlt_reproj2(Ms + v * 12, X, uvj[(size_t)v * J * 2], uvj[(size_t)v * J * 2 + 1], &depth);
+  return cost;
+}
+
+__global__ __launch_bounds__(256) void dlt_robust_kernel(const float* __restrict__ uv, const float* __restrict__ intr,
+                                                         const float* __restrict__ mat, const int* __restrict__ offs,
+                                                         float* __restrict__ out, unsigned char* __restrict__ inlier,
+                                                         int* __restrict__ count, float* __restrict__ resid, int J, int invert,
+                                                         double px2, int refine) {
+  __shared__ float Ms[DLT_ROBUST_MAX_VIEWS * 12];
+  const int b = blockIdx.x, lane = threadIdx.x & 63;
+  const int j = blockIdx.y * 4 + (threadIdx.x >> 6);
+  const int v0 = offs[b], N = offs[b + 1] - v0;                                   // block-uniform
+  const float qnan = __builtin_nanf("");
+  if (N < 2 || N > DLT_ROBUST_MAX_VIEWS) {
+    if (j < J) {
+      const size_t t = (size_t)b * J + j;
+      if (lane < 3) out[t * 3 + lane] = qnan;
+      if (lane == 0 && count) count[t] = 0;
+      for (int v = lane; v < N; v += 64) {
+        if (inlier) inlier[(size_t)(v0 + v) * J + j] = 0;
+        if (resid) resid[(size_t)(v0 + v) * J + j] = qnan;
+      }
+    }
+    return;
+  }
+  int bad = 0;
+  if ((int)threadIdx.x < N) {
+    float M[3][4];
+    dlt_view_matrix(intr, mat, v0 + (int)threadIdx.x, invert, M);
+    for (int r = 0; r < 3; ++r)
+      for (int c = 0; c < 4; ++c) { Ms[threadIdx.x * 12 + r * 4 + c] = M[r][c]; bad |= !(fabsf(M[r][c]) < INFINITY); }
+  }
+  bad = __syncthreads_or(bad);                                                    // (also the barrier behind the LDS writes)
+  if (j >= J) return;                                                             // spare waves of the last block row
+  const float* uvj = uv + ((size_t)v0 * J + j) * 2;                               // view v of this joint: uvj[v * J * 2 + {0, 1}]
+  const unsigned long long all = N == 64 ? ~0ull : (1ull << N) - 1ull;
+
+  // 1 + 2: pair hypotheses, each lane its best key
+  int bcnt = -1, bid = 0x7fffffff;
+  double bsum = 0.0;
+  unsigned long long bmask = 0;
+  if (!bad) {
+    const int npairs = N * (N - 1) / 2;
+    for (int p = lane; p < npairs; p += 64) {
+      int a = 0, rem = p;
+      while (rem >= N - 1 - a) { rem -= N - 1 - a; ++a; }                         // pairs in the order of a N + c
+      const int c = a + 1 + rem;
+      double X[3];
+      dlt_solve_mask(Ms, uvj, N, J, (1ull << a) | (1ull << c), X);
+      int cnt = 0;
+      double sum = 0.0;
+      unsigned long long mask = 0;
+      for (int v = 0; v < N; ++v) {
+        double depth;
+        const double r2 = dlt_reproj2(Ms + v * 12, X, uvj[(size_t)v * J * 2], uvj[(size_t)v * J * 2 + 1], &depth);
+        if (r2 < px2 && depth > 0.0) { ++cnt; sum += r2; mask |= 1ull << v; }
+      }
+      const int id = a * N + c;
+      if (cnt > bcnt || (cnt == bcnt && (sum < bsum || (sum == bsum && id < bid)))) { bcnt = cnt; bsum = sum; bid = id; bmask = mask; }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const int ocnt = __shfl_xor(bcnt, o, 64), oid = __shfl_xor(bid, o, 64);
+      const double osum = __shfl_xor(bsum, o, 64);
+      const unsigned long long omask = __shfl_xor(bmask, o, 64);
+      if (ocnt > bcnt || (ocnt == bcnt && (osum < bsum || (osum == bsum && oid < bid)))) { bcnt = ocnt; bsum = osum; bid = oid; bmask = omask; }
+    }
+  }
+
+  // 3: refit over the winner's inliers, or the plain solve
+  const bool fit = bcnt >= 2;
+  const unsigned long long over = fit ? bmask : all;
+  double X[3];
+  dlt_solve_mask(Ms, uvj, N, J, over, X);
+
+  // 4: Gauss-Newton on the summed r^2 of `over`
+  if (refine > 0) {
+    double cost = dlt_mask_cost(Ms, uvj, N, J, over, X);
+    for (int it = 0; it < refine; ++it) {
+      double A00 = 0, A01 = 0, A02 = 0, A11 = 0, A12 = 0, A22 = 0, g0 = 0, g1 = 0, g2 = 0;
+      for (int v = 0; v < N; ++v) {
+        if (!((over >> v) & 1ull)) continue;
+        const float* m = Ms + v * 12;
+        const double h0 = (double)m[0] * X[0] + (double)m[1] * X[1] + (double)m[2] * X[2] + (double)m[3];
+        const double h1 = (double)m[4] * X[0] + (double)m[5] * X[1] + (double)m[6] * X[2] + (double)m[7];
+        const double h2 = (double)m[8] * X[0] + (double)m[9] * X[1] + (double)m[10] * X[2] + (double)m[11];
+        const double pu = h0 / h2, pv = h1 / h2;
+        const double eu = pu - (double)uvj[(size_t)v * J * 2], ev = pv - (double)uvj[(size_t)v * J * 2 + 1];
+        const double ju0 = ((double)m[0] - pu * (double)m[8]) / h2, ju1 = ((double)m[1] - pu * (double)m[9]) / h2,
+                     ju2 = ((double)m[2] - pu * (double)m[10]) / h2;
+        const double jv0 = ((double)m[4] - pv * (double)m[8]) / h2, jv1 = ((double)m[5] - pv * (double)m[9]) / h2,
+                     jv2 = ((double)m[6] - pv * (double)m[10]) / h2;
+        A00 += ju0 * ju0 + jv0 * jv0; A01 += ju0 * ju1 + jv0 * jv1; A02 += ju0 * ju2 + jv0 * jv2;
+        A11 += ju1 * ju1 + jv1 * jv1; A12 += ju1 * ju2 + jv1 * jv2; A22 += ju2 * ju2 + jv2 * jv2;
+        g0 += ju0 * eu + jv0 * ev; g1 += ju1 * eu + jv1 * ev; g2 += ju2 * eu + jv2 * ev;
+      }
+      // (J^T J) d = -J^T e by the adjugate of the symmetric 3x3
+      const double c00 = A11 * A22 - A12 * A12, c01 = A02 * A12 - A01 * A22, c02 = A01 * A12 - A02 * A11;
+      const double c11 = A00 * A22 - A02 * A02, c12 = A01 * A02 - A00 * A12, c22 = A00 * A11 - A01 * A01;
+      const double det = A00 * c00 + A01 * c01 + A02 * c02;
+      const double Y[3] = {X[0] - (c00 * g0 + c01 * g1 + c02 * g2) / det, X[1] - (c01 * g0 + c11 * g1 + c12 * g2) / det,
+                           X[2] - (c02 * g0 + c12 * g1 + c22 * g2) / det};
+      const double trial = dlt_mask_cost(Ms, uvj, N, J, over, Y);
+      if (!(trial < cost)) break;                                                 // (a NaN trial stops here too)
+      X[0] = Y[0]; X[1] = Y[1]; X[2] = Y[2];
+      cost = trial;
+    }
+  }
+
+  // 5: outputs
+  const size_t t = (size_t)b * J + j;
+  if (lane < 3) out[t * 3 + lane] = (float)(lane == 0 ? X[0] : lane == 1 ? X[1] : X[2]);
+  if (lane == 0 && count) count[t] = fit ? bcnt : 0;
+  if (lane < N) {
+    const size_t e = (size_t)(v0 + lane) * J + j;
+    if (inlier) inlier[e] = fit ? (unsigned char)((bmask >> lane) & 1ull) : (unsigned char)0;
+    if (resid) {
+      double depth;
+      const float r = (float)sqrt(dlt_reproj2(Ms + lane * 12, X, uvj[(size_t)lane * J * 2], uvj[(size_t)lane * J * 2 + 1], &depth));
+      resid[e] = fabsf(r) < INFINITY ? r : qnan;
+    }
+  }
+}
+
+// B * J <= INT_MAX and J <= 4096: the entry point refuses more (the grid's second dimension is ceil(J / 4)).
+extern "C" hipError_t poem_launch_dlt_robust(const float* uv, const float* intr, const float* mat, const int* offs, float* out,
+                                             unsigned char* inlier, int* count, float* resid, int B, int J, int invert,
+                                             double inlier_px, int refine, hipStream_t s) {
+  if (J > 4096) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(dlt_robust_kernel, dim3(B, (J + 3) / 4), dim3(256), 0, s, uv, intr, mat, offs, out, inlier, count, resid, J,
+                     invert, inlier_px * inlier_px, refine);
   return hipGetLastError();
 }
 

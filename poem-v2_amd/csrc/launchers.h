@@ -126,6 +126,9 @@ hipError_t poem_launch_dlt(const float* uv, const float* intr, const float* mat,
 hipError_t poem_launch_dlt_confidence(const float* uv, const float* conf, const float* intr, const float* mat,
                                       const int* offs, float* out, int* sel_count, int B, int J, int invert, int mode,
                                       double threshold, hipStream_t s);
+hipError_t poem_launch_dlt_robust(const float* uv, const float* intr, const float* mat, const int* offs, float* out,
+                                  unsigned char* inlier, int* count, float* resid, int B, int J, int invert,
+                                  double inlier_px, int refine, hipStream_t s);
 hipError_t poem_launch_pa_epe(const float* pred, const float* gt, float* out, int B, int P, hipStream_t s);
 hipError_t poem_launch_pck_accumulate(const float* pred, const float* gt, int B, int P, double vmin, double vmax, int steps,
                                       unsigned int* counts, double* sum, unsigned int* n, float* dist_out, hipStream_t s);

@@ -270,6 +270,18 @@ int poem_dlt_confidence(const float* uv, const float* conf, const float* cam_int
   return POEM_OK;
 }
 
+int poem_dlt_robust(const float* uv, const float* cam_intr, const float* cam_mat, const int32_t* view_offsets, float* out_xyz,
+                    uint8_t* inlier, int32_t* inlier_count, float* reproj_px, int batch, int njoints, int invert,
+                    double inlier_px, int refine, void* stream) {
+  if (!uv || !cam_intr || !cam_mat || !view_offsets || !out_xyz || batch <= 0 || njoints <= 0 || njoints > 4096 || (invert & ~1))
+    return POEM_E_ARG;
+  if (!(inlier_px > 0.0) || refine < 0 || refine > 16) return POEM_E_ARG;  // (NaN refused; +inf: every view in front of the point)
+  if ((int64_t)batch * njoints > INT32_MAX) return POEM_E_ARG;             // the kernel indexes (sample, joint) in int
+  HIPCHK(poem_launch_dlt_robust(uv, cam_intr, cam_mat, view_offsets, out_xyz, inlier, inlier_count, reproj_px, batch, njoints,
+                                invert, inlier_px, refine, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 size_t poem_conv3x3_packed_bytes(int cout, int cin) {
   if (cout <= 0 || cin <= 0 || cin % 8) return 0;
   return poem_conv3x3_packed_floats(cout, cin) * sizeof(float);

@@ -101,6 +101,7 @@ SIGNATURES = {
     "poem_heatmap_uv": (_i, [_vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
     "poem_heatmap_uv_conf": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _f, _f, _vp]),
     "poem_dlt_confidence": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, ctypes.c_double, _vp]),
+    "poem_dlt_robust": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, ctypes.c_double, _i, _vp]),
     "poem_conv3x3_packed_bytes": (_sz, [_i, _i]),
     "poem_pack_conv3x3": (_i, [_vp, _i, _i, _vp, _vp]),
     "poem_conv3x3": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i64, _i, _i, _i, _vp]),

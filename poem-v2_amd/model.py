@@ -17,7 +17,7 @@ from .losses import LossMetric, PoemLoss
 from .triangulation import triangulate_reference_joints
 
 
-DLT_CONFIDENCE_MODES = ("off", "threshold", "weighted")
+DLT_CONFIDENCE_MODES = ("off", "threshold", "weighted", "ransac")
 
 
 def head_in_channels(backbone_name):
@@ -62,11 +62,18 @@ class PtEmbedMultiviewStereoV2:
         if cfg.get("MANO_ASSETS", None) and not cfg.HEAD.get("MANO_ASSETS", None):
             self.ptEmb_head.set_mano_assets(cfg.get("MANO_ASSETS"))
             self.ptEmb_head.mano_assets_source = f"config:{cfg.get('MANO_ASSETS')}"       # (a config key, not a caller's call)
-        # confidence-aware DLT (upstream's triangulate_dlt, lib/utils/triangulation.py:111-148): "off" | "threshold" | "weighted"
+        # confidence-aware DLT (upstream's triangulate_dlt, lib/utils/triangulation.py:111-148): "off" | "threshold" | "weighted";
+        # "ransac" (no upstream counterpart): views that disagree with the others' geometry are left out (triangulation.py).
+        # DLT_INLIER_PX: the inlier radius in image pixels; the default 8.0 is two heat-map pixels at 256^2 images with 64^2 maps
+        # and has NOT been measured on real data.  DLT_REFINE_ITERS: Gauss-Newton steps on the reprojection error (0..16)
         self.dlt_confidence = str(cfg.get("DLT_CONFIDENCE", "off")).lower()
         self.dlt_threshold = float(cfg.get("DLT_CONFIDENCE_THRESHOLD", 0.5))
+        self.dlt_inlier_px = float(cfg.get("DLT_INLIER_PX", 8.0))
+        self.dlt_refine_iters = int(cfg.get("DLT_REFINE_ITERS", 0))
         if self.dlt_confidence not in DLT_CONFIDENCE_MODES:
             raise ValueError(f"DLT_CONFIDENCE {self.dlt_confidence!r}: expected one of {DLT_CONFIDENCE_MODES}")
+        if not self.dlt_inlier_px > 0 or not 0 <= self.dlt_refine_iters <= 16:
+            raise ValueError(f"DLT_INLIER_PX = {self.dlt_inlier_px} must be > 0 and DLT_REFINE_ITERS = {self.dlt_refine_iters} in 0..16")
         self.decoders = None
         # optional LOSS node (POEM.py:41-45,125-146): the loss VALUE of a forward; absent -> compute_loss raises, nothing else changes
         self.loss = None
@@ -132,8 +139,8 @@ class PtEmbedMultiviewStereoV2:
         H, W = img.shape[-2:]
         img_feats = self.extract_img_feat(img)
         mlvl_feat = self.decoders.feat_decode(img_feats, self.img_backbone.name)            # :267
-        conf = None
-        if self.dlt_confidence == "off":
+        conf = inlier = reproj = None
+        if self.dlt_confidence in ("off", "ransac"):
             uv_pred = self.decoders.heatmap_stage(img_feats, W, H)                          # :270
         else:
             uv_pred, conf = self.decoders.heatmap_stage(img_feats, W, H, return_conf=True)
@@ -145,9 +152,14 @@ class PtEmbedMultiviewStereoV2:
             if views.min() < 2:
                 raise ValueError("a batch mixing single-view and multi-view samples has no DLT solution for the former "
                                  "(upstream's SVD returns the null vector of a rank-2 system there)")
-            ref_joints = triangulate_reference_joints(uv_pred, K, T, views, conf=conf,      # :284-299
-                                                      mode=None if conf is None else self.dlt_confidence,
-                                                      threshold=self.dlt_threshold)
+            if self.dlt_confidence == "ransac":
+                ref_joints, inlier, reproj = triangulate_reference_joints(uv_pred, K, T, views, mode="ransac",
+                                                                          inlier_px=self.dlt_inlier_px,
+                                                                          refine=self.dlt_refine_iters, return_inliers=True)
+            else:
+                ref_joints = triangulate_reference_joints(uv_pred, K, T, views, conf=conf,  # :284-299
+                                                          mode=None if conf is None else self.dlt_confidence,
+                                                          threshold=self.dlt_threshold)
         img_metas = {"inp_img_shape": (H, W), "cam_intr": K, "cam_extr": T, "master_id": batch["master_id"],
                      "cam_view_num": views}
         preds = self.ptEmb_head(mlvl_feat=mlvl_feat, img_metas=img_metas, reference_joints=ref_joints)
@@ -158,6 +170,8 @@ class PtEmbedMultiviewStereoV2:
                      pred_joints_uv=uv_pred, pred_ref_joints_3d=ref_joints)                 # :321-331
         if conf is not None:
             preds["pred_joints_conf"] = conf
+        if inlier is not None:
+            preds.update(pred_joints_inlier=inlier, pred_joints_reproj=reproj)
         return preds
 
     def testing_step(self, batch, step_idx=0, **kwargs):

@@ -7,7 +7,11 @@ whole ragged batch instead of a Python loop of per-sample ``torch.linalg.svd`` c
 
 Confidence-aware forms (``poem_heatmap_uv_conf`` + ``poem_dlt_confidence``): ``heatmap_to_uv(..., return_conf=True)`` also
 returns each joint's heat-map peak, ``triangulate_reference_joints(..., conf=, mode=)`` discounts views by it, and
-``triangulate_dlt`` keeps the name, arguments and result of upstream's one-sample function (triangulation.py:111-148)."""
+``triangulate_dlt`` keeps the name, arguments and result of upstream's one-sample function (triangulation.py:111-148).
+
+Outlier-robust form (``poem_dlt_robust``, ``mode="ransac"``): views whose 2-D joint disagrees with the geometry of the others are
+left out of the solve, with optional Gauss-Newton refinement of the reprojection error.  Upstream has nothing like it; its
+definition is ``include/poem_hip.h`` and the fp64 restatement in tests/dlt_robust_util.py."""
 import numpy as np
 import torch
 
@@ -33,7 +37,7 @@ def _offsets(views, device):
 
 
 def triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num, conf=None, mode=None, threshold=0.5,
-                                 return_count=False, invert=True):
+                                 return_count=False, invert=True, inlier_px=8.0, refine=0, return_inliers=False):
     """uv (BN,J,2) pixel coordinates per view, cam_intr (BN,3,3), cam_extr (BN,4,4) camera->master (the batch's
     ``target_cam_extr``), cam_view_num (B,) views per sample -> (B,J,3) joints in the master frame.
 
@@ -42,8 +46,20 @@ def triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num, conf=None
     joint's solve when ``conf`` (BN,J) > ``threshold``; the threshold drops by 0.05 until two views do, and stays lowered
     for the sample's following joints.  ``mode`` "weighted": each view's two rows are scaled by its confidence.
     ``return_count``: also the (B,J) int32 number of views each solve used.  ``invert=False``: ``cam_extr`` is already
-    master->camera.  Both run inside one stream-ordered launch."""
+    master->camera.  Both run inside one stream-ordered launch.
+
+    ``mode`` "ransac" (``poem_dlt_robust``; upstream has no counterpart, ``conf`` is not read): a view whose 2-D joint disagrees
+    with the geometry of the others is left out.  Every pair of the sample's views gives a hypothesis, a view within ``inlier_px``
+    pixels of its reprojection and in front of the camera is its inlier, the pair with the most inliers (ties: smaller summed
+    squared error, then the earlier pair) is solved again over its inliers; with fewer than two inliers, or a camera that is not
+    finite, the plain solve over all views stands.  ``refine`` (0..16) Gauss-Newton steps on the reprojection error follow.
+    Exhaustive and deterministic, 2..64 views per sample.  With three views and one outlier every pair explains itself and the
+    outlier is not identified: the mode needs three clean views.  ``return_count``: the (B,J) inlier counts (0 after the
+    fallback).  ``return_inliers``: ``(out, inlier (BN,J) bool, resid (BN,J) pixels)`` (``(out, count, inlier, resid)`` with both),
+    ``resid`` being the final joint's reprojection error in every view, inlier or not."""
     if not uv.is_cuda:
+        if mode == "ransac":
+            raise ValueError("mode 'ransac' takes device tensors: it runs on the MI355X HIP path only (no CPU fallback)")
         raise RuntimeError("triangulate_reference_joints runs on the MI355X HIP path only (no CPU fallback)")
     views = [int(v) for v in cam_view_num]
     BN, J = uv.shape[0], uv.shape[1]
@@ -53,6 +69,8 @@ def triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num, conf=None
     uv, cam_intr, cam_extr = f32(uv), f32(cam_intr), f32(cam_extr)
     out = torch.empty(len(views), J, 3, dtype=torch.float32, device=uv.device)
     offs = _offsets(views, uv.device)
+    if return_inliers and mode != "ransac":
+        raise ValueError("return_inliers needs mode 'ransac'")
     if mode in (None, "off"):
         if return_count:
             raise ValueError("return_count needs a confidence mode")
@@ -60,8 +78,22 @@ def triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num, conf=None
                                                  len(views), J, int(bool(invert)), hip.ptr(out), hip.stream()),
                   "poem_triangulate_dlt")
         return out
+    if mode == "ransac":
+        if max(views) > 64:
+            raise ValueError("mode 'ransac' takes at most 64 views per sample (the inlier set is one 64-bit mask)")
+        inlier_px, refine = float(inlier_px), int(refine)
+        if not inlier_px > 0 or not 0 <= refine <= 16:
+            raise ValueError("mode 'ransac' needs inlier_px > 0 (inf allowed) and refine in 0..16")
+        count = torch.empty(len(views), J, dtype=torch.int32, device=uv.device) if return_count else None
+        inl = torch.empty(BN, J, dtype=torch.uint8, device=uv.device) if return_inliers else None
+        resid = torch.empty(BN, J, dtype=torch.float32, device=uv.device) if return_inliers else None
+        hip.check(hip.lib().poem_dlt_robust(hip.ptr(uv), hip.ptr(cam_intr), hip.ptr(cam_extr), offs.data_ptr(), hip.ptr(out),
+                                            hip.ptr(inl, torch.uint8), hip.ptr(count, torch.int32), hip.ptr(resid), len(views), J,
+                                            int(bool(invert)), inlier_px, refine, hip.stream()), "poem_dlt_robust")
+        res = (out,) + ((count,) if return_count else ()) + ((inl.bool(), resid) if return_inliers else ())
+        return res if len(res) > 1 else out
     if mode not in hip.DLT_MODES:
-        raise ValueError(f"mode {mode!r}: expected None, 'off', 'threshold' or 'weighted'")
+        raise ValueError(f"mode {mode!r}: expected None, 'off', 'threshold', 'weighted' or 'ransac'")
     if conf is None or tuple(conf.shape) != (BN, J):
         raise ValueError(f"mode {mode!r} needs conf of shape ({BN}, {J})")
     threshold = float(threshold)
@@ -123,11 +155,15 @@ def heatmap_to_uv(uv_hmap, img_w, img_h, return_conf=False):
     return uv
 
 
-def reference_joints_from_heatmaps(uv_hmap, cam_intr, cam_extr, cam_view_num, img_w, img_h, mode=None, threshold=0.5):
+def reference_joints_from_heatmaps(uv_hmap, cam_intr, cam_extr, cam_view_num, img_w, img_h, mode=None, threshold=0.5,
+                                   inlier_px=8.0, refine=0):
     """Heat maps of every view -> per-view 2-D joints -> ragged DLT -> (B,J,3) reference joints: the two launches that
-    replace POEM.py:213-222 + :284-299 upstream.  ``mode`` / ``threshold`` as ``triangulate_reference_joints``: the
-    confidences are the maps' own peaks (still two launches)."""
+    replace POEM.py:213-222 + :284-299 upstream.  ``mode`` / ``threshold`` / ``inlier_px`` / ``refine`` as
+    ``triangulate_reference_joints``: the confidences are the maps' own peaks (still two launches); "ransac" reads none."""
     if mode in (None, "off"):
         return triangulate_reference_joints(heatmap_to_uv(uv_hmap, img_w, img_h), cam_intr, cam_extr, cam_view_num)
+    if mode == "ransac":
+        return triangulate_reference_joints(heatmap_to_uv(uv_hmap, img_w, img_h), cam_intr, cam_extr, cam_view_num, mode=mode,
+                                            inlier_px=inlier_px, refine=refine)
     uv, conf = heatmap_to_uv(uv_hmap, img_w, img_h, return_conf=True)
     return triangulate_reference_joints(uv, cam_intr, cam_extr, cam_view_num, conf=conf, mode=mode, threshold=threshold)

@@ -164,15 +164,32 @@ class BenchmarkScores:
                 "chamfer_mm": 0.5 * (m["chamfer_pred2gt"] + m["chamfer_gt2pred"]) * 1e3}
 
 
+class InlierFraction:
+    """``--dlt-confidence ransac``: the share of (view, joint) pairs the robust triangulation kept, summed on the device (no read-back
+    per batch) and reduced over ranks like the other metrics."""
+
+    def __init__(self, device):
+        self.acc = torch.zeros(2, dtype=torch.float64, device=device)           # (inliers, pairs)
+
+    def feed(self, inlier):
+        self.acc[0] += inlier.sum()
+        self.acc[1] += inlier.numel()
+
+    def result(self):
+        n, total = pdist.all_reduce_sum_(self.acc.clone()).tolist()       # (every rank calls it; the local sums stay)
+        return n / total if total else None
+
+
 def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, batch_size=2, seed=0, verbose=True,
              pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, mano_assets=None,
-             benchmark_scores=False):
+             benchmark_scores=False, dlt_inlier_px=8.0, dlt_refine=0):
     """``draw``: a ``DrawingHandCallback`` (rank 0, ``--draw --faces``) called with every batch.  This scope has no images: the panels
     show the meshes and skeletons over mid-grey views.  ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``)."""
     rank, _, world = pdist.env_world()
     if dlt_confidence != "off" and not pyramid:
-        raise SystemExit("--dlt-confidence reads the heat maps' peaks: it needs --pyramid or --shards (this scope starts "
+        raise SystemExit("--dlt-confidence reads the heat-map stage's output: it needs --pyramid or --shards (this scope starts "
                          "behind the heat-map stage)")
+    inlier_acc = InlierFraction(device) if dlt_confidence == "ransac" else None
     head_node = pk.CN(cfg["MODEL"]["HEAD"])
     head_node["MAX_VIEWS"] = max(10, int(view_range[1]))
     if mano_assets:
@@ -227,14 +244,18 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
             if decoders is not None:
                 pyr = [f.to(device) for f in pk.inputs.synthetic_pyramid(sum(views), seed=seed * 100003 + s)]
                 mlvl_feat = decoders.feat_decode(pyr)                                   # POEM.py:267
-                if dlt_confidence == "off":
+                if dlt_confidence in ("off", "ransac"):
                     uv_pred = decoders.heatmap_stage(pyr, 256, 256)                     # POEM.py:270
                 else:
                     uv_pred, conf = decoders.heatmap_stage(pyr, 256, 256, return_conf=True)
                 # random features carry no hand: keep the pipeline honest (the kernels run, their output is consumed)
                 # but triangulate a blend that stays near the synthetic joints so the head sees sane geometry
                 uv = uv + 1e-3 * (uv_pred - uv_pred.mean(dim=1, keepdim=True))
-            if min(views) >= 2 and dlt_confidence != "off":   # upstream's triangulate_dlt (lib/utils/triangulation.py:111-148)
+            if min(views) >= 2 and dlt_confidence == "ransac":   # views that disagree with the others' geometry are left out
+                rj, inl, _ = triangulate_reference_joints(uv, metas["cam_intr"], metas["cam_extr"], views, mode="ransac",
+                                                          inlier_px=dlt_inlier_px, refine=dlt_refine, return_inliers=True)
+                inlier_acc.feed(inl)
+            elif min(views) >= 2 and dlt_confidence != "off":   # upstream's triangulate_dlt (lib/utils/triangulation.py:111-148)
                 rj = triangulate_reference_joints(uv, metas["cam_intr"], metas["cam_extr"], views, conf=conf,
                                                   mode=dlt_confidence, threshold=dlt_threshold)
             elif min(views) >= 2:
@@ -278,6 +299,8 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
            "template_source": template_source}
     if bench_scores is not None:
         res["benchmark"] = bench_scores.result()
+    if inlier_acc is not None:
+        res["dlt_inlier_fraction"] = inlier_acc.result()
     return res
 
 
@@ -286,7 +309,8 @@ BACKBONE_TYPES = {"hrnet": "HRNet", "resnet18": "ResNet18", "resnet34": "ResNet3
 
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
                     n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
-                    mano_assets=None, backbone_engine="torch", backbone="hrnet", benchmark_scores=False):
+                    mano_assets=None, backbone_engine="torch", backbone="hrnet", benchmark_scores=False, dlt_inlier_px=8.0,
+                    dlt_refine=0):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -315,7 +339,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     head_node = dict(cfg["MODEL"]["HEAD"])
     head_node["MAX_VIEWS"] = max(10, int(view_range[1]))
     model_node = {"TYPE": "PtEmbedMultiviewStereoV2", "HEAD": head_node, "DATA_PRESET": {"CENTER_IDX": 9}, "DEVICE": str(device),
-                  "DLT_CONFIDENCE": dlt_confidence, "DLT_CONFIDENCE_THRESHOLD": dlt_threshold}
+                  "DLT_CONFIDENCE": dlt_confidence, "DLT_CONFIDENCE_THRESHOLD": dlt_threshold, "DLT_INLIER_PX": dlt_inlier_px,
+                  "DLT_REFINE_ITERS": dlt_refine}
     if losses is not None:
         model_node["LOSS"] = loss_node(cfg)
     if mano_assets:
@@ -348,6 +373,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         raise SystemExit("medium_MANO needs a MANO layer (licence-gated assets): pass --mano-assets FILE.npz")
     mpvpe, mpjpe = MeanEPE("verts", device=device), MeanEPE("joints", device=device)
     bench_scores = BenchmarkScores(device) if benchmark_scores else None
+    inlier_acc = InlierFraction(device) if dlt_confidence == "ransac" else None
     n, t0, frames, steps, t_draw = 0, None, [], [0], [0.0]
 
     def run(frames):
@@ -359,6 +385,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         gv = batch["master_verts_3d"].reshape(-1, 778, 3).to(device)
         mpjpe.feed(preds["pred_joints_3d"], gj)
         mpvpe.feed(preds["pred_verts_3d"], gv)
+        if inlier_acc is not None and "pred_joints_inlier" in preds:      # (absent when every sample has one view: no DLT)
+            inlier_acc.feed(preds["pred_joints_inlier"])
         if bench_scores is not None:
             bench_scores.feed(preds["pred_joints_3d"], gj, preds["pred_verts_3d"], gv)
         if losses is not None:                             # one launch + finalize, sums stay on the device (POEM.py:476,483 upstream)
@@ -396,6 +424,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         res["losses"] = model.loss_metric.reduce().get_measures()
     if bench_scores is not None:
         res["benchmark"] = bench_scores.result()
+    if inlier_acc is not None:
+        res["dlt_inlier_fraction"] = inlier_acc.result()
     return res
 
 
@@ -403,6 +433,7 @@ def main(args):
     view_range = [args.view_min, args.view_max]
     check_losses_args(args)
     mano_assets = getattr(args, "mano_assets", None)          # (absent from a build_parser() namespace)
+    robust = dict(dlt_inlier_px=getattr(args, "dlt_inlier_px", 8.0), dlt_refine=getattr(args, "dlt_refine", 0))
     if args.cfg and os.path.exists(args.cfg):
         with open(args.cfg, "r") as f:
             cfg = yaml.load(f, Loader=yaml.FullLoader)
@@ -447,12 +478,12 @@ def main(args):
                               losses=j_regressor, mano_assets=mano_assets,
                               backbone_engine=getattr(args, "backbone_engine", "torch"),
                               backbone=getattr(args, "backbone", "hrnet"),
-                              benchmark_scores=getattr(args, "benchmark_scores", False))
+                              benchmark_scores=getattr(args, "benchmark_scores", False), **robust)
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
                        dlt_confidence=args.dlt_confidence, dlt_threshold=args.dlt_threshold, draw=draw, mano_assets=mano_assets,
-                       benchmark_scores=getattr(args, "benchmark_scores", False))
+                       benchmark_scores=getattr(args, "benchmark_scores", False), **robust)
     if rank == 0:
         exp_id = f"{args.dataset}_view_{view_range[0]}_{view_range[1]}_{args.model}"
         if args.model == "huge":
@@ -485,9 +516,10 @@ def build_parser():
     parser.add_argument("--template", type=str, default=None, metavar="FILE",
                         help="(799,3) zero-pose hand template (.npy / .pt; ManoLayer's zero-pose joints + vertices, centred at "
                              "joint 9).  With --reload either this or --mano-assets is required; synthetic otherwise (this build).")
-    parser.add_argument("--dlt-confidence", choices=("off", "threshold", "weighted"), default="off",
+    parser.add_argument("--dlt-confidence", choices=("off", "threshold", "weighted", "ransac"), default="off",
                         help="Discount views by their heat-map peak in the DLT of the reference joints (model key DLT_CONFIDENCE; "
-                             "threshold = upstream's triangulate_dlt).  Needs --pyramid or --shards.")
+                             "threshold = upstream's triangulate_dlt), or (ransac, no upstream counterpart) leave out the views that "
+                             "disagree with the geometry of the others.  Needs --pyramid or --shards.")
     parser.add_argument("--dlt-threshold", type=float, default=0.5, help="confi_thres of --dlt-confidence threshold.")
     parser.add_argument("--batch_size", type=int, default=2, help="--val_batch_size of the reference (lib/opt.py:27-30).")
     parser.add_argument("--faces", type=str, default=None, metavar="FILE.npy",
@@ -517,6 +549,12 @@ def build_cli():
     parser.add_argument("--backbone", choices=tuple(BACKBONE_TYPES), default=argparse.SUPPRESS,
                         help="with --shards: the image backbone (default hrnet); sets MODEL.BACKBONE.TYPE and MODEL.HEAD.IN_CHANNELS "
                              "(160 / 128 / 512).")
+    parser.add_argument("--dlt-inlier-px", type=float, default=argparse.SUPPRESS,
+                        help="--dlt-confidence ransac: the inlier radius in image pixels (model key DLT_INLIER_PX; default 8.0 = two "
+                             "heat-map pixels at 256^2 images with 64^2 maps -- not measured on real data).")
+    parser.add_argument("--dlt-refine", type=int, default=argparse.SUPPRESS,
+                        help="--dlt-confidence ransac: Gauss-Newton steps on the reprojection error after the refit, 0..16 (model key "
+                             "DLT_REFINE_ITERS; default 0).  The result line gains \"dlt_inlier_fraction\".")
     parser.add_argument("--benchmark-scores", action="store_true", default=argparse.SUPPRESS,
                         help="add a \"benchmark\" block to the result line: the FreiHAND / HO3D leaderboard numbers -- mesh F@5 / F@15, raw "
                              "and Procrustes-aligned (PA_), the AUC of the aligned joints / vertices over 0..50 mm (pa_auc_j / pa_auc_v) "
