@@ -751,6 +751,65 @@ int poem_loss_terms(const float* coords, const float* pred_joints_uv, const floa
                     const float* j_regressor, const poem_loss_cfg_t* cfg, int batch, int total_views, double* out, void* workspace,
                     size_t workspace_bytes, void* stream);
 
+/* ---- baseline JPEG (csrc/jpeg.cpp, csrc/jpeg.h, csrc/jpeg.hip): the `image_<i>.jpg` members of a record shard without PIL ---------
+ * Replaces webdataset's decode("rgb8") for JPEG members (PIL -> libjpeg on one Python thread): the serial half (marker parsing,
+ * Huffman decoding) runs on host threads, the dense half (dequantisation, inverse DCT, chroma up-sampling, YCbCr -> RGB) on the
+ * device, and writes the interleaved uint8 pixels where poem_warp_affine reads them.  The arithmetic (csrc/jpeg.h) restates
+ * libjpeg's default path and gives PIL's bytes, or the image is REFUSED (status > 0) and the caller decodes it with PIL: refusing
+ * is never an error of the call.
+ * Accepted: SOF0 / SOF1, 8-bit samples, Huffman coding, ONE scan holding every component; 1 component, or 3 components taken as
+ *   YCbCr with luma sampling 1x1, 2x1 or 2x2 and both chroma components 1x1; 8-bit quantisation tables; DRI / RSTn; byte stuffing;
+ *   any APPn / COM segment (EXIF orientation is ignored, as Image.open ignores it).  Chroma is up-sampled as libjpeg does it: the
+ *   3:1 "fancy" taps where the component is more than 2 samples wide, plain replication in images of width <= 4.
+ * Refused: progressive, lossless, hierarchical or arithmetic-coded frames; 12-bit samples; 2 or 4 components; an Adobe APP14
+ *   segment whose transform is not 1 on a 3-component image, or 'R','G','B' component ids without an Adobe segment (libjpeg may
+ *   read either as RGB); any other sampling; 16-bit quantisation tables; a table a component names but no segment defined; a Huffman
+ *   table that is not a prefix code; a second frame header, DNL, or any marker the grammar does not allow where it stands; an
+ *   entropy stream that ends early, overruns a block, holds a DC value outside int16, lacks an expected RSTn or is not followed by
+ *   EOI; a height or width of 0 or above 65500; a block whose dequantised coefficients sum (in magnitude) above 5900 -- the range
+ *   guard derived in csrc/jpeg.h, beyond which libjpeg-turbo's 16-bit SIMD arithmetic and 32-bit arithmetic part ways.
+ * poem_jpeg_desc_t: one image of a call.  Coefficients are int16, de-zigzagged (natural order, row-major 8x8), block after block in
+ *   raster order of each component's block grid, component after component; the grids are padded to whole MCUs exactly as the scan
+ *   holds them (blocks_w / blocks_h; a 1-component image has ceil(w/8) x ceil(h/8)).  quant[c] is COMPONENT c's table, natural order.
+ * poem_jpeg_entropy_decode (host; no GPU is touched): n streams -> descs[n] and the coefficients, both in CALLER memory (pinned
+ *   staging).  Headers are parsed first and the images that pass are given consecutive 16-byte aligned coef_offsets; totals[0] is the
+ *   byte count that layout needs.  coef == NULL stops there (a size query: totals and the header fields of descs are valid);
+ *   otherwise POEM_E_WORKSPACE when coef_bytes < totals[0] (nothing written to coef), else the scans are decoded by `threads` host
+ *   threads (<= 0: 8; at most 16; a fixed number, never the machine's core count), image by image, each writing only its own
+ *   range.  An image refused at this stage keeps its range (unused).  After it block_base / quad_base are the prefix sums over the
+ *   images taken, totals = {coef bytes, blocks, quads, images taken}: a quad is a run of 4 pixels of one row, h * ceil(w / 4) per
+ *   image.  Every read is checked against lengths[i], every write against coef_bytes.  The result does not depend on `threads`.
+ *   status: 0 taken, 1 unsupported format, 2 malformed stream, 3 range guard.  POEM_E_ARG: NULL pointers, n <= 0, a negative length,
+ *   coef off 16 bytes; POEM_E_UNSUPPORTED: n > 65535 (poem_warp_affine's limit), or no host memory for the n frame states.
+ * poem_jpeg_reconstruct (device): descs, coef, out_offsets in DEVICE memory as uploaded; image i is written as (h, w, 3) uint8 RGB
+ *   (a 1-component image replicated) at out + out_offsets[i]; refused images are skipped and nothing else of `out` is touched.  An
+ *   image whose descriptor is inconsistent, whose coefficients end past coef_bytes or whose pixels end past out_bytes is skipped
+ *   too.  Any alignment of out and the offsets will do (dword stores where a row segment sits on 4 bytes, byte stores elsewhere).
+ *   workspace: poem_jpeg_workspace_bytes(total_blocks) = 64 total_blocks bytes for the uint8 component planes, 16-byte aligned;
+ *   POEM_E_WORKSPACE when NULL or short.  total_blocks / total_quads = totals[1], totals[2].  POEM_E_ARG: NULL pointers, n <= 0,
+ *   negative totals, misaligned coef / workspace (16).  POEM_E_UNSUPPORTED: n > 65535, or 2^24 workgroups or more in a launch (above
+ *   32 (2^24 - 1) blocks or 256 (2^24 - 1) quads: about 2800 views of 640x480).  Nothing to do (no image taken) is POEM_OK without a launch; total_quads = 0 with blocks runs the inverse DCT
+ *   alone (the planes stay in the workspace; tools/bench_jpeg.py times the two kernels that way).  All offsets are 64-bit.
+ * poem_jpeg_reconstruct_host: the same through plain loops over csrc/jpeg.h, host memory, no GPU: pins the arithmetic to PIL where
+ *   there is no device, and is what tools/jpeg_hostcheck.cpp drives under the sanitizers. */
+typedef struct poem_jpeg_desc {
+  int32_t status;                    /* 0 taken; > 0 refused (see above) */
+  int32_t height, width, ncomp;      /* ncomp 1 | 3 */
+  int32_t hs, vs;                    /* luma sampling factors: 1,1 | 2,1 | 2,2 */
+  int32_t blocks_w[3], blocks_h[3];  /* block grid of each component, padded to whole MCUs */
+  int64_t coef_offset, coef_bytes;   /* this image's range in the coefficient buffer (bytes; offset on 16) */
+  int64_t block_base, quad_base;     /* blocks / quads of the images taken before this one */
+  uint16_t quant[3][64];
+} poem_jpeg_desc_t;
+int poem_jpeg_entropy_decode(const uint8_t* const* streams, const int64_t* lengths, int n, poem_jpeg_desc_t* descs, int16_t* coef,
+                             int64_t coef_bytes, int64_t* totals, int threads);
+size_t poem_jpeg_workspace_bytes(int64_t total_blocks);
+int poem_jpeg_reconstruct(const poem_jpeg_desc_t* descs, const int16_t* coef, int64_t coef_bytes, const int64_t* out_offsets,
+                          uint8_t* out, int64_t out_bytes, int n, int64_t total_blocks, int64_t total_quads, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int poem_jpeg_reconstruct_host(const poem_jpeg_desc_t* descs, const int16_t* coef, int64_t coef_bytes, const int64_t* out_offsets,
+                               uint8_t* out, int64_t out_bytes, int n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -6,7 +6,7 @@ registers them, as ``import lib.models`` does upstream)."""
 from .config import CN  # noqa: F401
 from .builder import (HEAD, TRANSFORMER, BACKBONE, MODEL, Registry, build_from_cfg, build_head, build_transformer,  # noqa: F401
                       build_backbone, build_model)
-from . import builder, weights, inputs, hip, configs, triangulation, decode, backbone, resnet, transform, wds, mano, render, losses  # noqa: F401
+from . import builder, weights, inputs, hip, configs, triangulation, decode, backbone, resnet, jpeg, transform, wds, mano, render, losses  # noqa: F401
 from .transformer import PtEmbedTRv4  # noqa: F401
 from .head import POEM_Generalized_Head  # noqa: F401
 from .backbone import HRNet  # noqa: F401
@@ -14,6 +14,7 @@ from .resnet import ResNet18, ResNet34, ResNet50  # noqa: F401
 from .model import PtEmbedMultiviewStereoV2  # noqa: F401
 from .transform import TRANSFORM, SimpleTransform3DMultiView, build_transform  # noqa: F401
 from .wds import MultiviewWebDataset, MixWebDataset, collation_random_n_views  # noqa: F401
+from .jpeg import EncodedImage  # noqa: F401
 from .mano import ManoLayer  # noqa: F401
 from .hip import make_basis  # noqa: F401
 from .render import MeshRenderer, DrawingHandCallback, draw_skeleton, project_to_views, save_png  # noqa: F401

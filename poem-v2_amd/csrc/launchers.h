@@ -4,6 +4,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "../../include/poem_hip.h"   // poem_jpeg_desc_t
 #include "chain.h"
 #include "conv.h"
 #include "loss.h"
@@ -141,6 +142,10 @@ hipError_t poem_launch_mano_to_openpose(const float* jreg, const float* verts, f
 hipError_t poem_launch_warp_affine(const unsigned char* src, const long long* src_off, const int* src_hw,
                                    const double* minv, const double* gain, float* out_f32, unsigned char* out_u8, int views,
                                    int OH, int OW, hipStream_t s);
+// csrc/jpeg.hip
+hipError_t poem_launch_jpeg_reconstruct(const poem_jpeg_desc_t* descs, const int16_t* coef, long long coef_bytes,
+                                        const long long* out_offsets, unsigned char* out, long long out_bytes, int n,
+                                        long long total_blocks, long long total_quads, unsigned char* planes, hipStream_t s);
 hipError_t poem_launch_heatmap_uv(const float* hmap, float* uv, int maps, int hh, int hw, float img_w, float img_h,
                                   hipStream_t s);
 hipError_t poem_launch_heatmap_uv_conf(const float* hmap, float* uv, float* conf, int maps, int hh, int hw, float img_w,

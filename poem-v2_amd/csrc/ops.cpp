@@ -605,6 +605,24 @@ int poem_warp_affine(const uint8_t* src, const int64_t* src_offsets, const int32
   return POEM_OK;
 }
 
+// ---- baseline JPEG (csrc/jpeg.hip; the host half, poem_jpeg_entropy_decode / poem_jpeg_reconstruct_host, is csrc/jpeg.cpp) --------
+size_t poem_jpeg_workspace_bytes(int64_t total_blocks) { return total_blocks > 0 ? (size_t)total_blocks * 64 : 0; }
+
+int poem_jpeg_reconstruct(const poem_jpeg_desc_t* descs, const int16_t* coef, int64_t coef_bytes, const int64_t* out_offsets,
+                          uint8_t* out, int64_t out_bytes, int n, int64_t total_blocks, int64_t total_quads, void* workspace,
+                          size_t workspace_bytes, void* stream) {
+  if (!descs || !coef || !out_offsets || !out || n <= 0 || coef_bytes < 0 || out_bytes < 0 || total_blocks < 0 || total_quads < 0)
+    return POEM_E_ARG;
+  if (((uintptr_t)descs & 15) || ((uintptr_t)coef & 15) || ((uintptr_t)out_offsets & 7) || ((uintptr_t)workspace & 15)) return POEM_E_ARG;
+  // at most 2^24 - 1 workgroups of 256 threads per launch: below 2^32 threads, what the runtime guarantees
+  if (n > 65535 || total_blocks > (((int64_t)1 << 24) - 1) * 32 || total_quads > (((int64_t)1 << 24) - 1) * 256) return POEM_E_UNSUPPORTED;
+  if (total_blocks == 0 && total_quads == 0) return POEM_OK;                 // no image taken: nothing to write
+  if (total_blocks > 0 && (!workspace || workspace_bytes < poem_jpeg_workspace_bytes(total_blocks))) return POEM_E_WORKSPACE;
+  HIPCHK(poem_launch_jpeg_reconstruct(descs, coef, coef_bytes, (const long long*)out_offsets, out, out_bytes, n, total_blocks,
+                                      total_quads, (unsigned char*)workspace, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 // ---- mesh rendering (csrc/render.hip) ------------------------------------------------------------------------------------------
 // workspace of a render: six floats per (mesh, view, vertex) -- linear in the view count, so that the number of views a workspace
 // holds can be read back from its size (the view count itself, view_offsets[batch], lives on the device)

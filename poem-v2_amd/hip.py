@@ -153,6 +153,10 @@ SIGNATURES = {
     "poem_loss_workspace_bytes": (_sz, [_i, _i]),
     "poem_loss_terms": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(PoemLossCfg), _i, _i, _vp,
                              _vp, _sz, _vp]),
+    "poem_jpeg_entropy_decode": (_i, [_vp, _vp, _i, _vp, _vp, _i64, _vp, _i]),
+    "poem_jpeg_workspace_bytes": (_sz, [_i64]),
+    "poem_jpeg_reconstruct": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i64, _i64, _vp, _sz, _vp]),
+    "poem_jpeg_reconstruct_host": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i]),
 }
 
 _LIB = None

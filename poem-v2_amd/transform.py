@@ -11,6 +11,7 @@ frame: closed-form crop matrices for all views at once (:func:`crop_geometry`) i
 No CPU fallback: without the HIP library / a GPU the image side raises (``hip.lib()``); the label side
 (:meth:`SimpleTransform3DMultiView.labels`) is pure numpy and runs anywhere.
 """
+import ctypes
 import math
 import random
 
@@ -19,6 +20,7 @@ import torch
 
 from . import hip
 from .builder import Registry, build_from_cfg
+from .jpeg import DESC_BYTES, EncodedImage, JpegDesc
 
 TRANSFORM = Registry("transform")                     # lib/utils/builder.py:311 upstream
 NUM_JOINTS = 21                                       # CONST.NUM_JOINTS
@@ -129,48 +131,121 @@ class _Staging:
 _staging = {}
 
 
+# ---- JPEG handles (jpeg.EncodedImage) in warp_views -------------------------------------------------------------------
+JPEG_THREADS = 8                                      # host threads of poem_jpeg_entropy_decode: a fixed number (library maximum 16)
+_jpeg_counts = {"taken": 0, "refused": 0}
+
+
+def jpeg_counts():
+    """Handles :func:`warp_views` has decoded on the device (``taken``) and handed to PIL (``refused``) since the last reset."""
+    return dict(_jpeg_counts)
+
+
+def reset_jpeg_counts():
+    _jpeg_counts["taken"] = _jpeg_counts["refused"] = 0
+
+
+def set_jpeg_threads(n):
+    global JPEG_THREADS
+    JPEG_THREADS = max(1, min(16, int(n)))
+
+
+def _pad16(n):
+    return (n + 15) & ~15
+
+
+def _jpeg_call(lib, streams, descs, coef, coef_bytes, totals):
+    n = len(streams)
+    bufs = [np.frombuffer(d, np.uint8) for d in streams]
+    ptrs = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bufs])
+    lens = (ctypes.c_int64 * n)(*[len(d) for d in streams])
+    hip.check(lib.poem_jpeg_entropy_decode(ptrs, lens, n, descs, coef, coef_bytes, totals, JPEG_THREADS), "poem_jpeg_entropy_decode")
+
+
 def warp_views(images, affines, out_size, gains=None, device="cuda:0", out="f32"):
-    """images: list of uint8 (H_i, W_i, 3) arrays (ragged sizes); affines: per view a (2,3) / (3,3) source->destination
-    matrix (what the reference hands to ``cv2.warpAffine``); out_size = (W, H); gains: per view 3 colour gains or None.
+    """images: list of uint8 (H_i, W_i, 3) arrays (ragged sizes) and / or ``jpeg.EncodedImage`` handles; affines: per view a
+    (2,3) / (3,3) source->destination matrix (what the reference hands to ``cv2.warpAffine``); out_size = (W, H); gains: per view
+    3 colour gains or None.
     -> device tensor (V,3,H,W) fp32 = warped / 255 - 0.5  (``out="f32"``)  or  (V,H,W,3) uint8  (``out="u8"``).
-    One pinned upload and one kernel launch for all views."""
+    One pinned upload and one warp launch for all views.  Handles are Huffman-decoded on host threads straight into the pinned
+    buffer (coefficients, not pixels), uploaded with the arrays in that one copy and reconstructed on the device
+    (``poem_jpeg_reconstruct``) into the blob the warp reads: their pixels never exist on the host.  A handle the library refuses
+    is decoded by PIL and treated as an array; :func:`jpeg_counts` tells which route ran."""
     lib = hip.lib()
     dev = torch.device(device)
     if dev.type != "cuda":
         raise RuntimeError("warp_views runs on the GPU only (there is no CPU fallback)")
+    images = list(images)
     V = len(images)
     if V == 0 or len(affines) != V:
         raise ValueError("warp_views needs one affine per image and at least one image")
+    if out not in ("f32", "u8"):
+        raise ValueError("out must be 'f32' or 'u8'")
     ow, oh = int(out_size[0]), int(out_size[1])
     head = V * (8 + 8 + 48 + 24)
     head = (head + 15) & ~15
-    offs, total = [], head
+    handles = [i for i, im in enumerate(images) if isinstance(im, EncodedImage)]
+    nh = len(handles)
     for im in images:
-        if im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3:
+        if not isinstance(im, EncodedImage) and (im.dtype != np.uint8 or im.ndim != 3 or im.shape[2] != 3):
             raise ValueError("images must be uint8 (H, W, 3)")
-        offs.append(total - head)
-        total += (im.size + 15) & ~15
+    # staging: tables | descriptors | reconstruct's offsets | coefficients | array pixels.  ONE library call parses and decodes the
+    # handles; room for their coefficients is bounded from the sizes in their headers, and room is asked for every handle's pixels
+    # too: one the library refuses is decoded by PIL after all and uploaded as an array.
+    desc_at = head
+    joff_at = desc_at + nh * DESC_BYTES
+    coef_at = _pad16(joff_at + 8 * nh)
+    coef_room = sum(_pad16(images[i].coef_bound) for i in handles)
     st = _staging.setdefault(dev.index or 0, _Staging())
-    slot, pinned = st.take(total)
+    slot, pinned = st.take(coef_at + coef_room + sum(_pad16(im.size) for im in images))
     host = pinned.numpy()
+    totals = (ctypes.c_int64 * 4)()
+    coef_need = 0
+    if nh:
+        descs = (JpegDesc * nh).from_buffer(host, desc_at)
+        _jpeg_call(lib, [images[i].data for i in handles], descs, host.ctypes.data + coef_at, coef_room, totals)
+        coef_need = int(totals[0])
+        for i, d in zip(handles, descs):
+            if d.status != 0:
+                images[i] = images[i].decode()
+                _jpeg_counts["refused"] += 1
+            else:
+                _jpeg_counts["taken"] += 1
+        del descs
+    pix_at = coef_at + coef_need
+    offs, up_total = [None] * V, pix_at
+    for v, im in enumerate(images):                     # arrays: in the upload
+        if not isinstance(im, EncodedImage):
+            offs[v] = up_total - head
+            host[up_total:up_total + im.size] = np.ascontiguousarray(im).reshape(-1)
+            up_total += _pad16(im.size)
+    total = up_total
+    for v, im in enumerate(images):                     # handles taken: device-only regions behind it
+        if isinstance(im, EncodedImage):
+            offs[v] = total - head
+            total += _pad16(im.size)
     host[0:8 * V].view(np.int64)[:] = offs
     host[8 * V:16 * V].view(np.int32)[:] = np.asarray([[im.shape[0], im.shape[1]] for im in images], np.int32).reshape(-1)
     host[16 * V:64 * V].view(np.float64)[:] = np.asarray([invert_affine(np.asarray(a)[:2]) for a in affines]).reshape(-1)
     if gains is not None:
         host[64 * V:88 * V].view(np.float64)[:] = np.asarray(gains, np.float64).reshape(-1)
-    for im, o in zip(images, offs):
-        host[head + o:head + o + im.size] = np.ascontiguousarray(im).reshape(-1)
+    if nh:
+        host[joff_at:joff_at + 8 * nh].view(np.int64)[:] = [offs[i] for i in handles]
     with torch.cuda.device(dev):
         blob = torch.empty(total, dtype=torch.uint8, device=dev)
-        blob.copy_(pinned[:total], non_blocking=True)
+        blob[:up_total].copy_(pinned[:up_total], non_blocking=True)
         ev = torch.cuda.Event()
         ev.record()
         st.ev[slot] = ev
         base = blob.data_ptr()
+        if nh and totals[3] > 0:
+            planes = torch.empty(lib.poem_jpeg_workspace_bytes(totals[1]), dtype=torch.uint8, device=dev)
+            hip.check(lib.poem_jpeg_reconstruct(base + desc_at, base + coef_at, coef_need, base + joff_at, base + head, total - head, nh,
+                                                totals[1], totals[2], planes.data_ptr(), planes.numel(), hip.stream()),
+                      "poem_jpeg_reconstruct")
+            planes.record_stream(torch.cuda.current_stream())
         f32 = torch.empty(V, 3, oh, ow, dtype=torch.float32, device=dev) if out == "f32" else None
         u8 = torch.empty(V, oh, ow, 3, dtype=torch.uint8, device=dev) if out == "u8" else None
-        if f32 is None and u8 is None:
-            raise ValueError("out must be 'f32' or 'u8'")
         hip.check(lib.poem_warp_affine(base + head, base, base + 8 * V, base + 16 * V,
                                        base + 64 * V if gains is not None else None, hip.ptr(f32) if f32 is not None else None,
                                        hip.ptr(u8, torch.uint8) if u8 is not None else None, V, oh, ow, hip.stream()), "poem_warp_affine")
@@ -302,7 +377,8 @@ class SimpleTransform3DMultiView:
 
     def labels(self, image, label, **kwargs):
         """One view: draw, then the label arithmetic (pure numpy, runs anywhere)."""
-        return self.frame_labels([image], [label], [self.draw(label, kwargs.get("no_rot", False), np.shape(image)[:2])])[0]
+        shape = image.shape if hasattr(image, "shape") else np.shape(image)          # (a JPEG handle knows its shape undecoded)
+        return self.frame_labels([image], [label], [self.draw(label, kwargs.get("no_rot", False), tuple(shape[:2]))])[0]
 
     # -- pixels -----------------------------------------------------------------------------------------------------------
     def images(self, results_list):

@@ -12,6 +12,10 @@ Mirrors ``lib/data_wds/multiview_wds.py`` (``MultiviewWebDataset``: :27-147), ``
 Decoding follows webdataset's ``decode("rgb8")``: images through PIL -> RGB uint8 (H, W, 3); ``.pyd`` through pickle.
 The per-view image work (mirror warp, crop / warp / normalise) runs on the GPU, one launch per frame
 (``transform.SimpleTransform3DMultiView.images``) or one per batch (``defer_images=True`` + ``collation_random_n_views``).
+
+``image_decode="device"`` (opt-in; the default ``"host"`` is PIL as above) leaves the JPEG members undecoded
+(:class:`EncodedImage`): ``transform.warp_views`` then Huffman-decodes them on host threads and reconstructs them on the GPU,
+bit-equal to PIL or not at all (a stream the library refuses goes through PIL there).
 """
 import io
 import json
@@ -25,6 +29,7 @@ import numpy as np
 import torch
 
 from .config import CN
+from .jpeg import EncodedImage
 from .transform import build_transform, warp_views
 
 INV_EXTR_DATASETS = ['Interhand', 'Arctic', 'Oakink', 'Oakink2']         # multiview_wds.py:14
@@ -98,8 +103,12 @@ def decode_rgb8(data):
         return np.asarray(im.convert("RGB"), dtype=np.uint8)
 
 
-def decode_record(rec):
-    """webdataset ``decode("rgb8")``: images -> uint8 (H, W, 3); pyd / json / txt / cls / npy by extension."""
+def decode_record(rec, images="host"):
+    """webdataset ``decode("rgb8")``: images -> uint8 (H, W, 3); pyd / json / txt / cls / npy by extension.
+    ``images="device"``: ``.jpg`` / ``.jpeg`` members stay :class:`EncodedImage` handles (shape from the header, pixels on demand);
+    every other image format is decoded here as before."""
+    if images not in ("host", "device"):
+        raise ValueError("images must be 'host' or 'device'")
     out = {}
     for k, v in rec.items():
         if k.startswith("__"):
@@ -107,7 +116,7 @@ def decode_record(rec):
             continue
         ext = k.rsplit(".", 1)[-1]
         if ext in IMAGE_EXTS:
-            out[k] = decode_rgb8(v)
+            out[k] = EncodedImage(v) if images == "device" and ext in ("jpg", "jpeg") else decode_rgb8(v)
         elif ext in ("pyd", "pickle"):
             out[k] = pickle.loads(v)
         elif ext in ("json", "jsn"):
@@ -151,10 +160,14 @@ class MultiviewWebDataset:
     TRANSFORM``, ``data_preset``, ``is_train``); iterating yields processed frames (``process_data_item``).
 
     ``defer_images=True`` leaves the pixels of a frame un-warped (``raw_image`` / ``affine`` / ``color_gain`` lists) so
-    that ``collation_random_n_views`` can warp every view of the batch in one launch."""
+    that ``collation_random_n_views`` can warp every view of the batch in one launch.  ``image_decode="device"`` keeps JPEG views
+    encoded until that launch (``decode_record(images="device")``); a view that gets an occlusion patch is materialised on the
+    host, as its pixels are written there."""
 
-    def __init__(self, cfg, data_preset=None, is_train=True, defer_images=False, rank=None, world=None):
-        self.cfg, self.is_train, self.defer_images = cfg, is_train, defer_images
+    def __init__(self, cfg, data_preset=None, is_train=True, defer_images=False, rank=None, world=None, image_decode="host"):
+        if image_decode not in ("host", "device"):
+            raise ValueError("image_decode must be 'host' or 'device'")
+        self.cfg, self.is_train, self.defer_images, self.image_decode = cfg, is_train, defer_images, image_decode
         self.urls, self.data_split = cfg.URLS, cfg.DATA_SPLIT
         self.epoch_size = cfg.get("EPOCH_SIZE", None)
         self.data_preset = cfg.DATA_PRESET if data_preset is None else data_preset
@@ -172,7 +185,7 @@ class MultiviewWebDataset:
         shards = list(self.shards)
         if self.is_train:
             random.shuffle(shards)
-        frames = (decode_record(r) for url in shards for r in tar_records(url))
+        frames = (decode_record(r, images=self.image_decode) for url in shards for r in tar_records(url))
         if self.is_train:
             frames = _buffer_shuffle(frames, 1000)                          # dataset.shuffle(1000), multiview_wds.py:51-52
         n = 0
@@ -244,7 +257,7 @@ class MultiviewWebDataset:
         pixels = [cams[c] for c in keep]
         if labels.get("request_flip", False):
             pixels = self._mirrored(pixels, [lab["cam_intr"] for lab in view_labels], [lab["raw_size"] for lab in view_labels])
-        draws = [self.transform.draw(lab, no_rot=(c == master), image_shape=np.shape(px)[:2]) for lab, c, px in zip(view_labels, keep, pixels)]
+        draws = [self.transform.draw(lab, no_rot=(c == master), image_shape=tuple(px.shape[:2])) for lab, c, px in zip(view_labels, keep, pixels)]
         views = self.transform.frame_labels(pixels, view_labels, draws)
         extr = self.remaster_extrinsics([lab["cam_extr"] for lab in view_labels], [v["extr_prerot"] for v in views])
         for v, lab, e in zip(views, view_labels, extr):

@@ -310,7 +310,7 @@ BACKBONE_TYPES = {"hrnet": "HRNet", "resnet18": "ResNet18", "resnet34": "ResNet3
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
                     n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
                     mano_assets=None, backbone_engine="torch", backbone="hrnet", benchmark_scores=False, dlt_inlier_px=8.0,
-                    dlt_refine=0):
+                    dlt_refine=0, image_decode="host"):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -321,6 +321,9 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     ``losses``: MANO's (16,778) joint regressor (``--losses --j-regressor``): every batch's loss terms (upstream's ``compute_loss``,
     value only) feed the model's ``loss_metric`` on the device and the result gains their batch-size-weighted averages.
     ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``), as ``evaluate`` does.
+    ``image_decode``: ``"device"`` keeps the records' JPEG views encoded up to the batch's warp launch (Huffman decoding on host
+    threads, reconstruction on the GPU, bit-equal to PIL; ``wds.EncodedImage``) and adds ``jpeg_device_fraction`` to the result: the
+    share of those views the device route took (the rest went through PIL).
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
     shards of the same record layout are written there first."""
     rank, _, world = pdist.env_world()
@@ -335,7 +338,9 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
             pk.wds.write_shard(u, [synthetic_frame(si * per + i, n_cams=n_cams, raw=raw_size) for i in range(per)])
     pdist.barrier()
     node = pk.wds.dataset_cfg(pattern, view_range=view_range, device=str(device))
-    dset = pk.MultiviewWebDataset(node, data_preset=node.DATA_PRESET, is_train=False, defer_images=True, rank=rank, world=world)
+    dset = pk.MultiviewWebDataset(node, data_preset=node.DATA_PRESET, is_train=False, defer_images=True, rank=rank, world=world,
+                                  image_decode=image_decode)
+    pk.transform.reset_jpeg_counts()
     head_node = dict(cfg["MODEL"]["HEAD"])
     head_node["MAX_VIEWS"] = max(10, int(view_range[1]))
     model_node = {"TYPE": "PtEmbedMultiviewStereoV2", "HEAD": head_node, "DATA_PRESET": {"CENTER_IDX": 9}, "DEVICE": str(device),
@@ -426,6 +431,10 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         res["benchmark"] = bench_scores.result()
     if inlier_acc is not None:
         res["dlt_inlier_fraction"] = inlier_acc.result()
+    if image_decode == "device":
+        counts = pk.transform.jpeg_counts()
+        seen = counts["taken"] + counts["refused"]
+        res["jpeg_device_fraction"] = counts["taken"] / seen if seen else None      # None: the shards hold no JPEG view
     return res
 
 
@@ -478,7 +487,8 @@ def main(args):
                               losses=j_regressor, mano_assets=mano_assets,
                               backbone_engine=getattr(args, "backbone_engine", "torch"),
                               backbone=getattr(args, "backbone", "hrnet"),
-                              benchmark_scores=getattr(args, "benchmark_scores", False), **robust)
+                              benchmark_scores=getattr(args, "benchmark_scores", False),
+                              image_decode=getattr(args, "image_decode", "host"), **robust)
     else:
         res = evaluate(cfg, view_range, args.model, device, reload=args.reload, epoch_size=args.epoch_size,
                        batch_size=args.batch_size, pyramid=args.pyramid, template=args.template,
@@ -559,6 +569,10 @@ def build_cli():
                         help="add a \"benchmark\" block to the result line: the FreiHAND / HO3D leaderboard numbers -- mesh F@5 / F@15, raw "
                              "and Procrustes-aligned (PA_), the AUC of the aligned joints / vertices over 0..50 mm (pa_auc_j / pa_auc_v) "
                              "and the symmetric mean nearest-vertex distance (chamfer_mm) -- computed on the device.")
+    parser.add_argument("--image-decode", choices=("host", "device"), default=argparse.SUPPRESS,
+                        help="with --shards: who decodes the records' JPEG views -- host (PIL, the default) or device (Huffman decoding on "
+                             "host threads, inverse DCT / up-sampling / colour on the GPU, bit-equal to PIL; a stream the device route "
+                             "refuses falls back to PIL).  device adds jpeg_device_fraction to the result line.")
     return parser
 
 
