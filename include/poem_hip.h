@@ -810,6 +810,63 @@ int poem_jpeg_reconstruct(const poem_jpeg_desc_t* descs, const int16_t* coef, in
 int poem_jpeg_reconstruct_host(const poem_jpeg_desc_t* descs, const int16_t* coef, int64_t coef_bytes, const int64_t* out_offsets,
                                uint8_t* out, int64_t out_bytes, int n);
 
+/* ---- baseline JPEG, Huffman decoding on the device (csrc/jpeg_entropy.h, csrc/jpeg_entropy.hip; opt-in) ------------------------------
+ * The entropy stage of the route above without host threads: the host only parses the headers and packs the entropy-coded bytes
+ * (about a fifth of the coefficients' size) for the upload; the device decodes them into the coefficient buffer poem_jpeg_reconstruct
+ * reads.  A serial bit stream is decoded in parallel by cutting each image's segment into SUBSEQUENCES of `subseq` raw bytes (a
+ * power of two, 16..1024; 0 = the default, 64) and iterating every subsequence's entry state to the fixed point, which is the
+ * serial decoder's state by induction whatever the stream; poem_jpeg_entropy_decode is the yardstick:
+ * status 0 exactly where it gives 0, the same coefficient bytes where taken, header-stage statuses equal (the same parser).  Which
+ * of 2 / 3 a damaged scan gets may differ where it breaks two rules.
+ * poem_jpeg_scan_t: one image's scan.  poem_jpeg_huff_t: one Huffman table as the decoders read it (9-bit look-up, then maxcode /
+ *   valoff), 1424 bytes.  An image's distinct tables (at most 6) stand at tables[table_base ...]; dc_sel / ac_sel index them per
+ *   component.
+ * poem_jpeg_entropy_prepare (host; no GPU is touched): parses n streams' headers.  descs / totals[0..3] come out exactly as from
+ *   poem_jpeg_entropy_decode's size query; scans[n]; totals[4] = bytes of the packed segments (each image's runs from its first
+ *   entropy-coded byte to the END of its stream, on 16 bytes), totals[5] = tables, totals[6] = subsequences of the call, totals[7]
+ *   = the most of one image.  packed == NULL stops there (tables may be NULL too); else POEM_E_WORKSPACE when packed_bytes <
+ *   totals[4] or table_room < totals[5] (nothing written), else tables and bytes are copied.  Images refused at the header stage
+ *   get an empty scan.  POEM_E_ARG: NULL pointers, n <= 0, a negative length or room, subseq not as above, packed off 16 bytes;
+ *   POEM_E_UNSUPPORTED: n > 65535 or no host memory.
+ * poem_jpeg_entropy_device: everything in DEVICE memory as uploaded.  Zeroes coef[0 .. coef_bytes), decodes, turns DC differences
+ *   into predictions and applies the range guard; status[i] (int32, device) gets every image's status and descs[i].status the same,
+ *   so that poem_jpeg_reconstruct skips what was refused here.  One workgroup of wg_threads lanes (64..1024, a multiple of 64;
+ *   0 = 1024) per image converges with barriers only: no workgroup waits for another.  Every stream read is bounded by the scan's own
+ *   byte range inside packed_bytes, every store by the image's own block range inside coef_bytes, every workspace index by
+ *   total_subs; a scan record or descriptor that does not hang together refuses its image.  The first n int32 of the workspace
+ *   hold the rounds each image took.  poem_jpeg_entropy_workspace_bytes(n, total_subs) says how large it must be (16-byte
+ *   aligned).  POEM_E_ARG: NULL pointers, n <= 0, negative sizes, subseq / wg_threads not as above, coef / packed / workspace off
+ *   16 bytes; POEM_E_WORKSPACE: workspace NULL or short; POEM_E_UNSUPPORTED: n > 65535.
+ * poem_jpeg_entropy_parallel_host: the SAME algorithm in plain loops over csrc/jpeg_entropy.h (fixed point, prefix sum, write pass,
+ *   DC pass, block pass), host memory, arguments as poem_jpeg_entropy_decode plus subseq and rounds[n] (may be NULL): where there
+ *   is no device it pins the algorithm to the serial decoder, and tools/jpeg_entropycheck.cpp drives it under the sanitizers. */
+typedef struct poem_jpeg_huff {
+  uint16_t look[512];                /* 9-bit prefix -> (length << 8) | symbol; 0: longer than 9 bits, or no such code */
+  int32_t maxcode[18];               /* largest code of each length (-1: none); [17] = sentinel */
+  int32_t valoff[17];                /* index of the first symbol of a length minus its first code */
+  uint8_t vals[256];
+  int32_t reserved;
+} poem_jpeg_huff_t;
+typedef struct poem_jpeg_scan {
+  int64_t byte_offset, byte_count;   /* the segment in the packed buffer (offset on 16) */
+  int64_t sub_base;                  /* subsequences of the images before this one */
+  int32_t sub_count;                 /* ceil(byte_count / subseq) */
+  int32_t restart;                   /* DRI: MCUs per restart interval, 0 = none */
+  int32_t table_base, table_count;
+  uint8_t dc_sel[3], ac_sel[3];      /* per component: which of the image's tables */
+  uint8_t reserved[2];
+} poem_jpeg_scan_t;
+int poem_jpeg_entropy_prepare(const uint8_t* const* streams, const int64_t* lengths, int n, int subseq, poem_jpeg_desc_t* descs,
+                              poem_jpeg_scan_t* scans, poem_jpeg_huff_t* tables, int64_t table_room, uint8_t* packed,
+                              int64_t packed_bytes, int64_t* totals);
+size_t poem_jpeg_entropy_workspace_bytes(int n, int64_t total_subs);
+int poem_jpeg_entropy_device(poem_jpeg_desc_t* descs, const poem_jpeg_scan_t* scans, const poem_jpeg_huff_t* tables,
+                             int64_t table_count, const uint8_t* packed, int64_t packed_bytes, int n, int subseq, int wg_threads,
+                             int64_t total_subs, int64_t total_blocks, int16_t* coef, int64_t coef_bytes, int32_t* status,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int poem_jpeg_entropy_parallel_host(const uint8_t* const* streams, const int64_t* lengths, int n, int subseq, poem_jpeg_desc_t* descs,
+                                    int16_t* coef, int64_t coef_bytes, int64_t* totals, int32_t* rounds);
+
 #ifdef __cplusplus
 }
 #endif

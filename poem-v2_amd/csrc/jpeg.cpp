@@ -11,6 +11,7 @@
 #include <vector>
 #include "../../include/poem_hip.h"
 #include "jpeg.h"
+#include "jpeg_entropy.h"
 
 namespace {
 
@@ -308,9 +309,246 @@ int decode_scan(const uint8_t* data, size_t len, const Frame& f, const poem_jpeg
   return TAKEN;
 }
 
+// Headers of all streams of a call -> frames, descs (status, geometry, consecutive 16-byte aligned coef_offsets).  -> the bytes
+// that layout needs.  Shared by the serial route and the parallel one: the header-stage refusals are the same by construction.
+int64_t layout_headers(const uint8_t* const* streams, const int64_t* lengths, int n, std::vector<Frame>& frames, poem_jpeg_desc_t* descs) {
+  int64_t need = 0;
+  for (int i = 0; i < n; ++i) {
+    poem_jpeg_desc_t& d = descs[i];
+    std::memset(&d, 0, sizeof(d));
+    d.status = parse_headers(streams[i], (size_t)lengths[i], frames[(size_t)i]);
+    if (d.status != TAKEN) continue;
+    fill_geometry(frames[(size_t)i], d);
+    d.coef_offset = need;
+    need += (d.coef_bytes + 15) & ~(int64_t)15;
+  }
+  return need;
+}
+
+// block_base / quad_base over the images taken, and totals[0..3]
+void finish_totals(poem_jpeg_desc_t* descs, int n, int64_t need, int64_t* totals) {
+  int64_t blocks = 0, quads = 0, taken = 0;
+  for (int i = 0; i < n; ++i) {
+    poem_jpeg_desc_t& d = descs[i];
+    d.block_base = blocks; d.quad_base = quads;
+    if (d.status != TAKEN) continue;
+    blocks += d.coef_bytes / 128;
+    quads += (int64_t)d.height * ((d.width + 3) / 4);
+    ++taken;
+  }
+  totals[0] = need; totals[1] = blocks; totals[2] = quads; totals[3] = taken;
+}
+
+// ---- the parallel entropy decoder, host side (csrc/jpeg_entropy.h) ---------------------------------------------------------------
+void compact_huff(const Huff& h, poem_jpeg_huff_t& t) {
+  std::memset(&t, 0, sizeof(t));
+  std::memcpy(t.look, h.look, sizeof(t.look));
+  t.maxcode[0] = -1;
+  for (int l = 1; l <= 17; ++l) t.maxcode[l] = h.maxcode[l];
+  t.valoff[0] = 0;
+  for (int l = 1; l <= 16; ++l) t.valoff[l] = h.valoff[l];
+  std::memcpy(t.vals, h.vals, sizeof(t.vals));
+}
+
+// The distinct tables the scan of a frame names, DC ones first (at most 3 + 3) -> their count; out may be NULL.
+int select_tables(const Frame& f, poem_jpeg_huff_t* out, uint8_t* dc_sel, uint8_t* ac_sel) {
+  int count = 0, slot_of[2][4];
+  for (int cls = 0; cls < 2; ++cls) {
+    for (int t = 0; t < 4; ++t) slot_of[cls][t] = -1;
+    for (int c = 0; c < f.ncomp; ++c) {
+      const int id = cls ? f.ta[c] : f.td[c];
+      if (slot_of[cls][id] < 0) {
+        if (out) compact_huff(cls ? f.ac[id] : f.dc[id], out[count]);
+        slot_of[cls][id] = count++;
+      }
+      (cls ? ac_sel : dc_sel)[c] = (uint8_t)slot_of[cls][id];
+    }
+  }
+  return count;
+}
+
+bool subseq_ok(int s) { return s >= 16 && s <= 1024 && (s & (s - 1)) == 0; }
+
+// One image through the parallel algorithm in plain loops: what a workgroup of csrc/jpeg_entropy.hip does, lane after lane.
+// seg: the entropy-coded segment up to the end of the stream.  -> status; rounds: fixed-point rounds taken.
+int parallel_scan(const uint8_t* seg, int64_t n, const Frame& f, const poem_jpeg_desc_t& d, int S, int16_t* coef, int32_t& rounds) {
+  std::memset(coef, 0, (size_t)d.coef_bytes);
+  rounds = 0;
+  poem_jpeg_huff_t tabs[6];
+  uint8_t dc_sel[3] = {0, 0, 0}, ac_sel[3] = {0, 0, 0};
+  select_tables(f, tabs, dc_sel, ac_sel);
+  JpegScanCtx c;
+  jpeg_scan_geometry(d, c);
+  c.data = seg; c.n = n; c.zigzag = kZigzag; c.restart = f.restart;
+  for (int k = 0; k < 3; ++k) { c.dc[k] = &tabs[dc_sel[k]]; c.ac[k] = &tabs[ac_sel[k]]; }
+  const int64_t nsub = (n + S - 1) / S;
+  std::vector<JpegSubState> entry((size_t)nsub), exit_((size_t)nsub), where((size_t)nsub);
+  std::vector<int32_t> blocks((size_t)nsub, 0), ev((size_t)nsub, JPEG_EV_RUN);
+  std::vector<int64_t> base((size_t)nsub + 1, 0);
+  std::vector<uint8_t> cur((size_t)nsub, 1), next((size_t)nsub, 0);
+  for (int64_t i = 0; i < nsub; ++i) entry[(size_t)i] = JpegSubState{i * S * 8, 0, 0};
+  JpegNoSink none;
+  for (bool any = nsub > 0; any;) {
+    any = false;
+    ++rounds;
+    for (int64_t i = 0; i < nsub; ++i) {                       // every lane whose entry changed decodes again, writing nothing
+      if (!cur[(size_t)i]) continue;
+      JpegSubState st = entry[(size_t)i];
+      int done = 0, e = JPEG_EV_RUN;
+      if (st.bit >= 0) e = jpeg_sub_decode(c, st, (i + 1) * S * 8, false, done, none);
+      if (e != JPEG_EV_RUN) { where[(size_t)i] = st; st = JpegSubState{(i + 1) * S * 8, 0, 0}; }   // an event: the next lane keeps its guess
+      exit_[(size_t)i] = st;
+      blocks[(size_t)i] = done; ev[(size_t)i] = e;
+    }
+    for (int64_t i = 0; i < nsub; ++i) {                       // its exit state becomes the next lane's entry
+      if (!cur[(size_t)i]) continue;
+      cur[(size_t)i] = 0;
+      if (i + 1 < nsub && !jpeg_state_eq(exit_[(size_t)i], entry[(size_t)i + 1])) {
+        entry[(size_t)i + 1] = exit_[(size_t)i];
+        next[(size_t)i + 1] = 1;
+        any = true;
+      }
+    }
+    cur.swap(next);
+  }
+  // the first event of the converged trace (what lies behind it was decoded from guesses and counts for nothing), then the first
+  // block of every subsequence
+  int event = JPEG_EV_RUN;
+  JpegSubState at{0, 0, 0};
+  int64_t event_sub = -1;
+  for (int64_t i = 0; i < nsub; ++i)
+    if (ev[(size_t)i] != JPEG_EV_RUN) { event = ev[(size_t)i]; at = where[(size_t)i]; event_sub = i; break; }
+  int64_t sum = 0;
+  for (int64_t i = 0; i < nsub; ++i) { base[(size_t)i] = sum; sum += blocks[(size_t)i]; }
+  int status = TAKEN;
+  for (int64_t i = 0; i < (event_sub >= 0 ? event_sub + 1 : nsub); ++i) {       // the write pass, up to the event
+    if (entry[(size_t)i].bit < 0) continue;
+    JpegCoefSink sink;
+    sink.start(&c, coef, base[(size_t)i]);
+    JpegSubState st = entry[(size_t)i];
+    int done = 0;
+    jpeg_sub_decode(c, st, (i + 1) * S * 8, false, done, sink);
+    if (sink.err) status = sink.err;
+  }
+  const int fin = jpeg_finish(c, event, at, event_sub >= 0 ? base[(size_t)event_sub] + blocks[(size_t)event_sub] : 0, coef);
+  if (fin) status = fin;
+  if (status) return status;
+  // the DC pass: differences -> predictions, per component in MCU order, from zero at every restart interval
+  {
+    JpegCoefSink walk;
+    walk.start(&c, coef, 0);
+    int64_t pred[3] = {0, 0, 0};
+    for (int64_t mcu = 0; mcu < c.total_mcus; ++mcu) {
+      if (c.restart && mcu && mcu % c.restart == 0) pred[0] = pred[1] = pred[2] = 0;
+      for (int slot = 0; slot < c.bpm; ++slot, walk.next_block()) {
+        const int comp = slot < c.hs * c.vs ? 0 : slot - c.hs * c.vs + 1;
+        pred[comp] += walk.blk[0];
+        if (pred[comp] < -32768 || pred[comp] > 32767) return MALFORMED;
+        walk.blk[0] = (int16_t)pred[comp];
+      }
+    }
+  }
+  // the block pass: the range guard
+  const int16_t* blk = coef;
+  for (int comp = 0; comp < d.ncomp; ++comp)
+    for (int64_t b = 0; b < (int64_t)d.blocks_w[comp] * d.blocks_h[comp]; ++b, blk += 64) {
+      int64_t l1 = 0;
+      for (int k = 0; k < 64; ++k) l1 += (int64_t)std::abs((int)blk[k]) * d.quant[comp][k];
+      if (l1 > POEM_JPEG_L1_MAX) return RANGE;
+    }
+  return TAKEN;
+}
+
 }  // namespace
 
 extern "C" {
+
+int poem_jpeg_entropy_prepare(const uint8_t* const* streams, const int64_t* lengths, int n, int subseq, poem_jpeg_desc_t* descs,
+                              poem_jpeg_scan_t* scans, poem_jpeg_huff_t* tables, int64_t table_room, uint8_t* packed,
+                              int64_t packed_bytes, int64_t* totals) {
+  if (!streams || !lengths || !descs || !scans || !totals || n <= 0) return POEM_E_ARG;
+  if (subseq == 0) subseq = 64;
+  if (!subseq_ok(subseq) || (packed && (!tables || table_room < 0 || packed_bytes < 0))) return POEM_E_ARG;
+  if (n > 65535) return POEM_E_UNSUPPORTED;
+  if ((uintptr_t)packed & 15) return POEM_E_ARG;
+  for (int i = 0; i < n; ++i)
+    if (!streams[i] || lengths[i] < 0) return POEM_E_ARG;
+  std::vector<Frame> frames;
+  try {
+    frames.resize((size_t)n);
+  } catch (const std::bad_alloc&) {
+    return POEM_E_UNSUPPORTED;
+  }
+  const int64_t need = layout_headers(streams, lengths, n, frames, descs);
+  finish_totals(descs, n, need, totals);
+  int64_t bytes = 0, ntab = 0, subs = 0, most = 0;
+  for (int i = 0; i < n; ++i) {
+    poem_jpeg_scan_t& s = scans[i];
+    std::memset(&s, 0, sizeof(s));
+    s.byte_offset = bytes; s.sub_base = subs; s.table_base = (int32_t)ntab;
+    if (descs[i].status != TAKEN) continue;
+    const Frame& f = frames[(size_t)i];
+    s.byte_count = lengths[i] - (int64_t)f.scan;
+    const int64_t ns = (s.byte_count + subseq - 1) / subseq;
+    if (ns > 0x7fffffff) return POEM_E_UNSUPPORTED;             // a stream of 32 GiB and more
+    s.sub_count = (int32_t)ns;
+    s.restart = f.restart;
+    s.table_count = select_tables(f, nullptr, s.dc_sel, s.ac_sel);
+    bytes += (s.byte_count + 15) & ~(int64_t)15;
+    ntab += s.table_count;
+    subs += ns;
+    if (ns > most) most = ns;
+  }
+  totals[4] = bytes; totals[5] = ntab; totals[6] = subs; totals[7] = most;
+  if (!packed) return POEM_OK;
+  if (packed_bytes < bytes || table_room < ntab) return POEM_E_WORKSPACE;
+  for (int i = 0; i < n; ++i) {
+    const poem_jpeg_scan_t& s = scans[i];
+    if (descs[i].status != TAKEN) continue;
+    uint8_t dc_sel[3], ac_sel[3];
+    select_tables(frames[(size_t)i], tables + s.table_base, dc_sel, ac_sel);
+    std::memcpy(packed + s.byte_offset, streams[i] + frames[(size_t)i].scan, (size_t)s.byte_count);
+    const int64_t padded = (s.byte_count + 15) & ~(int64_t)15;
+    std::memset(packed + s.byte_offset + s.byte_count, 0, (size_t)(padded - s.byte_count));
+  }
+  return POEM_OK;
+}
+
+int poem_jpeg_entropy_parallel_host(const uint8_t* const* streams, const int64_t* lengths, int n, int subseq, poem_jpeg_desc_t* descs,
+                                    int16_t* coef, int64_t coef_bytes, int64_t* totals, int32_t* rounds) {
+  if (!streams || !lengths || !descs || !totals || n <= 0 || (coef && coef_bytes < 0)) return POEM_E_ARG;
+  if (subseq == 0) subseq = 64;
+  if (!subseq_ok(subseq)) return POEM_E_ARG;
+  if (n > 65535) return POEM_E_UNSUPPORTED;
+  if ((uintptr_t)coef & 15) return POEM_E_ARG;
+  for (int i = 0; i < n; ++i)
+    if (!streams[i] || lengths[i] < 0) return POEM_E_ARG;
+  std::vector<Frame> frames;
+  try {
+    frames.resize((size_t)n);
+  } catch (const std::bad_alloc&) {
+    return POEM_E_UNSUPPORTED;
+  }
+  const int64_t need = layout_headers(streams, lengths, n, frames, descs);
+  finish_totals(descs, n, need, totals);
+  if (rounds) std::memset(rounds, 0, sizeof(int32_t) * (size_t)n);
+  if (!coef) return POEM_OK;
+  if (coef_bytes < need) return POEM_E_WORKSPACE;
+  try {
+    for (int i = 0; i < n; ++i) {
+      poem_jpeg_desc_t& d = descs[i];
+      if (d.status != TAKEN) continue;
+      const Frame& f = frames[(size_t)i];
+      int32_t r = 0;
+      d.status = parallel_scan(streams[i] + f.scan, lengths[i] - (int64_t)f.scan, f, d, subseq, coef + d.coef_offset / 2, r);
+      if (rounds) rounds[i] = r;
+    }
+  } catch (const std::bad_alloc&) {
+    return POEM_E_UNSUPPORTED;
+  }
+  finish_totals(descs, n, need, totals);
+  return POEM_OK;
+}
 
 int poem_jpeg_entropy_decode(const uint8_t* const* streams, const int64_t* lengths, int n, poem_jpeg_desc_t* descs, int16_t* coef,
                              int64_t coef_bytes, int64_t* totals, int threads) {
@@ -325,28 +563,8 @@ int poem_jpeg_entropy_decode(const uint8_t* const* streams, const int64_t* lengt
   } catch (const std::bad_alloc&) {
     return POEM_E_UNSUPPORTED;
   }
-  int64_t need = 0;
-  for (int i = 0; i < n; ++i) {
-    poem_jpeg_desc_t& d = descs[i];
-    std::memset(&d, 0, sizeof(d));
-    d.status = parse_headers(streams[i], (size_t)lengths[i], frames[(size_t)i]);
-    if (d.status != TAKEN) continue;
-    fill_geometry(frames[(size_t)i], d);
-    d.coef_offset = need;
-    need += (d.coef_bytes + 15) & ~(int64_t)15;
-  }
-  auto finish = [&]() {
-    int64_t blocks = 0, quads = 0, taken = 0;
-    for (int i = 0; i < n; ++i) {
-      poem_jpeg_desc_t& d = descs[i];
-      d.block_base = blocks; d.quad_base = quads;
-      if (d.status != TAKEN) continue;
-      blocks += d.coef_bytes / 128;
-      quads += (int64_t)d.height * ((d.width + 3) / 4);
-      ++taken;
-    }
-    totals[0] = need; totals[1] = blocks; totals[2] = quads; totals[3] = taken;
-  };
+  const int64_t need = layout_headers(streams, lengths, n, frames, descs);
+  auto finish = [&]() { finish_totals(descs, n, need, totals); };
   finish();
   if (!coef) return POEM_OK;
   if (coef_bytes < need) return POEM_E_WORKSPACE;

@@ -146,6 +146,12 @@ hipError_t poem_launch_warp_affine(const unsigned char* src, const long long* sr
 hipError_t poem_launch_jpeg_reconstruct(const poem_jpeg_desc_t* descs, const int16_t* coef, long long coef_bytes,
                                         const long long* out_offsets, unsigned char* out, long long out_bytes, int n,
                                         long long total_blocks, long long total_quads, unsigned char* planes, hipStream_t s);
+// csrc/jpeg_entropy.hip
+extern "C" size_t poem_jpeg_entropy_ws_bytes(int n, long long total_subs);
+extern "C" hipError_t poem_launch_jpeg_entropy(poem_jpeg_desc_t* descs, const poem_jpeg_scan_t* scans, const poem_jpeg_huff_t* tables,
+                                               long long table_count, const unsigned char* packed, long long packed_bytes, int n, int subseq,
+                                               int wg_threads, long long total_subs, long long total_blocks, int16_t* coef,
+                                               long long coef_bytes, int* status, void* workspace, hipStream_t s);
 hipError_t poem_launch_heatmap_uv(const float* hmap, float* uv, int maps, int hh, int hw, float img_w, float img_h,
                                   hipStream_t s);
 hipError_t poem_launch_heatmap_uv_conf(const float* hmap, float* uv, float* conf, int maps, int hh, int hw, float img_w,

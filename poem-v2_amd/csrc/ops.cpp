@@ -623,6 +623,29 @@ int poem_jpeg_reconstruct(const poem_jpeg_desc_t* descs, const int16_t* coef, in
   return POEM_OK;
 }
 
+// ---- Huffman decoding on the device (csrc/jpeg_entropy.hip; the host half, poem_jpeg_entropy_prepare / _parallel_host, is jpeg.cpp) ---
+size_t poem_jpeg_entropy_workspace_bytes(int n, int64_t total_subs) { return poem_jpeg_entropy_ws_bytes(n, total_subs); }
+
+int poem_jpeg_entropy_device(poem_jpeg_desc_t* descs, const poem_jpeg_scan_t* scans, const poem_jpeg_huff_t* tables,
+                             int64_t table_count, const uint8_t* packed, int64_t packed_bytes, int n, int subseq, int wg_threads,
+                             int64_t total_subs, int64_t total_blocks, int16_t* coef, int64_t coef_bytes, int32_t* status,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+  if (!descs || !scans || !tables || !packed || !coef || !status || n <= 0 || table_count < 0 || packed_bytes < 0 || total_subs < 0 ||
+      total_blocks < 0 || coef_bytes < 0)
+    return POEM_E_ARG;
+  if (subseq == 0) subseq = 64;                                  // the defaults: the best of the shapes measured (LABNOTES)
+  if (wg_threads == 0) wg_threads = 1024;
+  if (subseq < 16 || subseq > 1024 || (subseq & (subseq - 1)) || wg_threads < 64 || wg_threads > 1024 || (wg_threads & 63)) return POEM_E_ARG;
+  if (((uintptr_t)descs & 15) || ((uintptr_t)scans & 7) || ((uintptr_t)tables & 3) || ((uintptr_t)packed & 15) || ((uintptr_t)coef & 15) ||
+      ((uintptr_t)status & 3) || ((uintptr_t)workspace & 15))
+    return POEM_E_ARG;
+  if (n > 65535 || total_blocks > (((int64_t)1 << 24) - 1) * 32) return POEM_E_UNSUPPORTED;
+  if (!workspace || workspace_bytes < poem_jpeg_entropy_workspace_bytes(n, total_subs)) return POEM_E_WORKSPACE;
+  HIPCHK(poem_launch_jpeg_entropy(descs, scans, tables, table_count, packed, packed_bytes, n, subseq, wg_threads, total_subs, total_blocks,
+                                  coef, coef_bytes, status, workspace, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 // ---- mesh rendering (csrc/render.hip) ------------------------------------------------------------------------------------------
 // workspace of a render: six floats per (mesh, view, vertex) -- linear in the view count, so that the number of views a workspace
 // holds can be read back from its size (the view count itself, view_offsets[batch], lives on the device)

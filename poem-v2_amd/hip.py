@@ -157,6 +157,10 @@ SIGNATURES = {
     "poem_jpeg_workspace_bytes": (_sz, [_i64]),
     "poem_jpeg_reconstruct": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i, _i64, _i64, _vp, _sz, _vp]),
     "poem_jpeg_reconstruct_host": (_i, [_vp, _vp, _i64, _vp, _vp, _i64, _i]),
+    "poem_jpeg_entropy_prepare": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _i64, _vp, _i64, _vp]),
+    "poem_jpeg_entropy_workspace_bytes": (_sz, [_i, _i64]),
+    "poem_jpeg_entropy_device": (_i, [_vp, _vp, _vp, _i64, _vp, _i64, _i, _i, _i, _i64, _i64, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "poem_jpeg_entropy_parallel_host": (_i, [_vp, _vp, _i, _i, _vp, _vp, _i64, _vp, _vp]),
 }
 
 _LIB = None

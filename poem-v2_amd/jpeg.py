@@ -21,6 +21,19 @@ DESC_BYTES = ctypes.sizeof(JpegDesc)
 assert DESC_BYTES == 464
 
 
+class JpegScan(ctypes.Structure):
+    """include/poem_hip.h poem_jpeg_scan_t (the device entropy route)"""
+    _fields_ = [("byte_offset", ctypes.c_int64), ("byte_count", ctypes.c_int64), ("sub_base", ctypes.c_int64),
+                ("sub_count", ctypes.c_int32), ("restart", ctypes.c_int32), ("table_base", ctypes.c_int32),
+                ("table_count", ctypes.c_int32), ("dc_sel", ctypes.c_uint8 * 3), ("ac_sel", ctypes.c_uint8 * 3),
+                ("reserved", ctypes.c_uint8 * 2)]
+
+
+SCAN_BYTES = ctypes.sizeof(JpegScan)
+HUFF_BYTES = 1424                                            # sizeof(poem_jpeg_huff_t)
+assert SCAN_BYTES == 48
+
+
 def jpeg_size(data):
     """(height, width) from the frame header of a JPEG stream (any SOFn), without decoding; ValueError if there is none."""
     n, pos = len(data), 2
@@ -50,12 +63,13 @@ class EncodedImage:
     """An undecoded JPEG view: holds the bytes, knows its ``shape == (H, W, 3)`` from the header, and turns into PIL's pixels
     wherever an array is asked for (``np.asarray(handle)``, ``np.array(handle, copy=True)``) -- so host code that touches pixels
     (the occlusion patch, a user's own code) sees exactly what ``decode_rgb8`` gives today."""
-    __slots__ = ("data", "shape")
+    __slots__ = ("data", "shape", "entropy")
     dtype = np.dtype(np.uint8)
     ndim = 3
 
-    def __init__(self, data):
+    def __init__(self, data, entropy=None):
         self.data = bytes(data)
+        self.entropy = entropy                                   # "device": warp_views Huffman-decodes this view on the GPU
         h, w = jpeg_size(self.data)
         self.shape = (h, w, 3)
 

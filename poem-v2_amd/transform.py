@@ -20,7 +20,7 @@ import torch
 
 from . import hip
 from .builder import Registry, build_from_cfg
-from .jpeg import DESC_BYTES, EncodedImage, JpegDesc
+from .jpeg import DESC_BYTES, HUFF_BYTES, SCAN_BYTES, EncodedImage, JpegDesc, JpegScan
 
 TRANSFORM = Registry("transform")                     # lib/utils/builder.py:311 upstream
 NUM_JOINTS = 21                                       # CONST.NUM_JOINTS
@@ -133,16 +133,27 @@ _staging = {}
 
 # ---- JPEG handles (jpeg.EncodedImage) in warp_views -------------------------------------------------------------------
 JPEG_THREADS = 8                                      # host threads of poem_jpeg_entropy_decode: a fixed number (library maximum 16)
-_jpeg_counts = {"taken": 0, "refused": 0}
+JPEG_ENTROPY = "host"                                 # where handles are Huffman-decoded: "host" threads | "device" (opt-in)
+JPEG_SUBSEQ = 0                                       # device route: bytes per subsequence (0: the library's default) ...
+JPEG_WG_THREADS = 0                                   # ... and lanes of the workgroup that decodes one image (0: the default)
+_jpeg_counts = {"taken": 0, "refused": 0, "entropy_device": 0, "redone": 0}
+_entropy_route_ran = False
 
 
 def jpeg_counts():
-    """Handles :func:`warp_views` has decoded on the device (``taken``) and handed to PIL (``refused``) since the last reset."""
-    return dict(_jpeg_counts)
+    """Handles :func:`warp_views` has decoded on the device (``taken``) and handed to PIL (``refused``) since the last reset;
+    ``entropy_device``: handles whose coefficients the GPU produced; ``redone``: calls repeated on the host route because the
+    device refused a scan.  The last two are listed once the device entropy route has run since the last reset: where it never
+    runs the answer is the two counts it has always been."""
+    keys = _jpeg_counts if _entropy_route_ran else ("taken", "refused")
+    return {k: _jpeg_counts[k] for k in keys}
 
 
 def reset_jpeg_counts():
-    _jpeg_counts["taken"] = _jpeg_counts["refused"] = 0
+    global _entropy_route_ran
+    _entropy_route_ran = False
+    for k in _jpeg_counts:
+        _jpeg_counts[k] = 0
 
 
 def set_jpeg_threads(n):
@@ -150,19 +161,34 @@ def set_jpeg_threads(n):
     JPEG_THREADS = max(1, min(16, int(n)))
 
 
+def set_jpeg_entropy(where, subseq=None, wg_threads=None):
+    """Where :func:`warp_views` Huffman-decodes JPEG handles by default: ``"host"`` (threads, as ever) or ``"device"``."""
+    global JPEG_ENTROPY, JPEG_SUBSEQ, JPEG_WG_THREADS
+    if where not in ("host", "device"):
+        raise ValueError("jpeg entropy route must be 'host' or 'device'")
+    JPEG_ENTROPY = where
+    if subseq is not None:
+        JPEG_SUBSEQ = int(subseq)
+    if wg_threads is not None:
+        JPEG_WG_THREADS = int(wg_threads)
+
+
 def _pad16(n):
     return (n + 15) & ~15
 
 
-def _jpeg_call(lib, streams, descs, coef, coef_bytes, totals):
+def _jpeg_pointers(streams):
     n = len(streams)
     bufs = [np.frombuffer(d, np.uint8) for d in streams]
-    ptrs = (ctypes.c_void_p * n)(*[b.ctypes.data for b in bufs])
-    lens = (ctypes.c_int64 * n)(*[len(d) for d in streams])
-    hip.check(lib.poem_jpeg_entropy_decode(ptrs, lens, n, descs, coef, coef_bytes, totals, JPEG_THREADS), "poem_jpeg_entropy_decode")
+    return bufs, (ctypes.c_void_p * n)(*[b.ctypes.data for b in bufs]), (ctypes.c_int64 * n)(*[len(d) for d in streams])
 
 
-def warp_views(images, affines, out_size, gains=None, device="cuda:0", out="f32"):
+def _jpeg_call(lib, streams, descs, coef, coef_bytes, totals):
+    bufs, ptrs, lens = _jpeg_pointers(streams)
+    hip.check(lib.poem_jpeg_entropy_decode(ptrs, lens, len(streams), descs, coef, coef_bytes, totals, JPEG_THREADS), "poem_jpeg_entropy_decode")
+
+
+def warp_views(images, affines, out_size, gains=None, device="cuda:0", out="f32", jpeg_entropy=None):
     """images: list of uint8 (H_i, W_i, 3) arrays (ragged sizes) and / or ``jpeg.EncodedImage`` handles; affines: per view a
     (2,3) / (3,3) source->destination matrix (what the reference hands to ``cv2.warpAffine``); out_size = (W, H); gains: per view
     3 colour gains or None.
@@ -170,7 +196,27 @@ def warp_views(images, affines, out_size, gains=None, device="cuda:0", out="f32"
     One pinned upload and one warp launch for all views.  Handles are Huffman-decoded on host threads straight into the pinned
     buffer (coefficients, not pixels), uploaded with the arrays in that one copy and reconstructed on the device
     (``poem_jpeg_reconstruct``) into the blob the warp reads: their pixels never exist on the host.  A handle the library refuses
-    is decoded by PIL and treated as an array; :func:`jpeg_counts` tells which route ran."""
+    is decoded by PIL and treated as an array; :func:`jpeg_counts` tells which route ran.
+    ``jpeg_entropy="device"`` (default: a handle's own ``entropy`` mark, else the switch of :func:`set_jpeg_entropy`, ``"host"``)
+    uploads the entropy-coded bytes instead and Huffman-decodes them on the GPU (``poem_jpeg_entropy_device``); if the device
+    refuses any scan -- damaged files -- the whole call is done again on the host route."""
+    if jpeg_entropy is None:
+        jpeg_entropy = "device" if any(getattr(im, "entropy", None) == "device" for im in images) else JPEG_ENTROPY
+    if jpeg_entropy not in ("host", "device"):
+        raise ValueError("jpeg_entropy must be 'host' or 'device'")
+    images = list(images)
+    if jpeg_entropy == "device" and any(isinstance(im, EncodedImage) for im in images):
+        global _entropy_route_ran
+        _entropy_route_ran = True
+        res = _warp_views(images, affines, out_size, gains, device, out, True)
+        if res is not None:
+            return res
+        _jpeg_counts["redone"] += 1
+    return _warp_views(images, affines, out_size, gains, device, out, False)
+
+
+def _warp_views(images, affines, out_size, gains, device, out, entropy_device):
+    """:func:`warp_views` on one route; the device-entropy route returns None when a scan was refused."""
     lib = hip.lib()
     dev = torch.device(device)
     if dev.type != "cuda":
@@ -192,25 +238,46 @@ def warp_views(images, affines, out_size, gains=None, device="cuda:0", out="f32"
     # staging: tables | descriptors | reconstruct's offsets | coefficients | array pixels.  ONE library call parses and decodes the
     # handles; room for their coefficients is bounded from the sizes in their headers, and room is asked for every handle's pixels
     # too: one the library refuses is decoded by PIL after all and uploaded as an array.
+    # Device entropy: ... | scan records | Huffman tables | packed entropy-coded bytes | array pixels; the coefficients exist on the
+    # device only.  The header parse runs twice (a size query, then the fill): microseconds per image.
     desc_at = head
     joff_at = desc_at + nh * DESC_BYTES
     coef_at = _pad16(joff_at + 8 * nh)
-    coef_room = sum(_pad16(images[i].coef_bound) for i in handles)
+    totals = (ctypes.c_int64 * 8)()
+    if entropy_device:
+        streams = [images[i].data for i in handles]
+        bufs, ptrs, lens = _jpeg_pointers(streams)
+        scans_at, tables_at = coef_at, coef_at + nh * SCAN_BYTES
+        query = ((JpegDesc * nh)(), (JpegScan * nh)())
+        hip.check(lib.poem_jpeg_entropy_prepare(ptrs, lens, nh, JPEG_SUBSEQ, query[0], query[1], None, 0, None, 0, totals),
+                  "poem_jpeg_entropy_prepare")
+        ntab, packed_need = int(totals[5]), int(totals[4])
+        coef_at = tables_at + ntab * HUFF_BYTES                     # (the packed bytes stand where the coefficients would)
+        coef_room = packed_need
+    else:
+        coef_room = sum(_pad16(images[i].coef_bound) for i in handles)
     st = _staging.setdefault(dev.index or 0, _Staging())
     slot, pinned = st.take(coef_at + coef_room + sum(_pad16(im.size) for im in images))
     host = pinned.numpy()
-    totals = (ctypes.c_int64 * 4)()
     coef_need = 0
+    counts = {"taken": 0, "refused": 0}
     if nh:
         descs = (JpegDesc * nh).from_buffer(host, desc_at)
-        _jpeg_call(lib, [images[i].data for i in handles], descs, host.ctypes.data + coef_at, coef_room, totals)
-        coef_need = int(totals[0])
+        if entropy_device:
+            scans = (JpegScan * nh).from_buffer(host, scans_at)
+            hip.check(lib.poem_jpeg_entropy_prepare(ptrs, lens, nh, JPEG_SUBSEQ, descs, scans, host.ctypes.data + tables_at, ntab,
+                                                    host.ctypes.data + coef_at, coef_room, totals), "poem_jpeg_entropy_prepare")
+            coef_need = packed_need
+            del scans
+        else:
+            _jpeg_call(lib, [images[i].data for i in handles], descs, host.ctypes.data + coef_at, coef_room, totals)
+            coef_need = int(totals[0])
         for i, d in zip(handles, descs):
             if d.status != 0:
                 images[i] = images[i].decode()
-                _jpeg_counts["refused"] += 1
+                counts["refused"] += 1
             else:
-                _jpeg_counts["taken"] += 1
+                counts["taken"] += 1
         del descs
     pix_at = coef_at + coef_need
     offs, up_total = [None] * V, pix_at
@@ -239,11 +306,30 @@ def warp_views(images, affines, out_size, gains=None, device="cuda:0", out="f32"
         st.ev[slot] = ev
         base = blob.data_ptr()
         if nh and totals[3] > 0:
+            coef_ptr, coef_bytes = base + coef_at, coef_need
+            if entropy_device:
+                # the coefficients are produced here; the statuses come back in one small copy: the one synchronisation of the call
+                coef_bytes = int(totals[0])
+                coef = torch.empty(max(coef_bytes, 16), dtype=torch.uint8, device=dev)
+                status = torch.empty(nh, dtype=torch.int32, device=dev)
+                work = torch.empty(lib.poem_jpeg_entropy_workspace_bytes(nh, totals[6]), dtype=torch.uint8, device=dev)
+                hip.check(lib.poem_jpeg_entropy_device(base + desc_at, base + scans_at, base + tables_at, ntab, base + coef_at, packed_need,
+                                                       nh, JPEG_SUBSEQ, JPEG_WG_THREADS, totals[6], totals[1], coef.data_ptr(), coef_bytes,
+                                                       status.data_ptr(), work.data_ptr(), work.numel(), hip.stream()),
+                          "poem_jpeg_entropy_device")
+                got = status.cpu().tolist()
+                if any(g != 0 for i, g in zip(handles, got) if isinstance(images[i], EncodedImage)):       # a scan-stage refusal
+                    blob.record_stream(torch.cuda.current_stream())
+                    return None
+                coef_ptr = coef.data_ptr()
+                _jpeg_counts["entropy_device"] += counts["taken"]
             planes = torch.empty(lib.poem_jpeg_workspace_bytes(totals[1]), dtype=torch.uint8, device=dev)
-            hip.check(lib.poem_jpeg_reconstruct(base + desc_at, base + coef_at, coef_need, base + joff_at, base + head, total - head, nh,
+            hip.check(lib.poem_jpeg_reconstruct(base + desc_at, coef_ptr, coef_bytes, base + joff_at, base + head, total - head, nh,
                                                 totals[1], totals[2], planes.data_ptr(), planes.numel(), hip.stream()),
                       "poem_jpeg_reconstruct")
             planes.record_stream(torch.cuda.current_stream())
+        _jpeg_counts["taken"] += counts["taken"]
+        _jpeg_counts["refused"] += counts["refused"]
         f32 = torch.empty(V, 3, oh, ow, dtype=torch.float32, device=dev) if out == "f32" else None
         u8 = torch.empty(V, oh, ow, 3, dtype=torch.uint8, device=dev) if out == "u8" else None
         hip.check(lib.poem_warp_affine(base + head, base, base + 8 * V, base + 16 * V,

@@ -106,9 +106,11 @@ def decode_rgb8(data):
 def decode_record(rec, images="host"):
     """webdataset ``decode("rgb8")``: images -> uint8 (H, W, 3); pyd / json / txt / cls / npy by extension.
     ``images="device"``: ``.jpg`` / ``.jpeg`` members stay :class:`EncodedImage` handles (shape from the header, pixels on demand);
-    every other image format is decoded here as before."""
-    if images not in ("host", "device"):
-        raise ValueError("images must be 'host' or 'device'")
+    every other image format is decoded here as before.  ``images="device-entropy"``: the same handles, marked so that
+    ``transform.warp_views`` also Huffman-decodes them on the GPU."""
+    if images not in ("host", "device", "device-entropy"):
+        raise ValueError("images must be 'host', 'device' or 'device-entropy'")
+    mark = "device" if images == "device-entropy" else None
     out = {}
     for k, v in rec.items():
         if k.startswith("__"):
@@ -116,7 +118,7 @@ def decode_record(rec, images="host"):
             continue
         ext = k.rsplit(".", 1)[-1]
         if ext in IMAGE_EXTS:
-            out[k] = EncodedImage(v) if images == "device" and ext in ("jpg", "jpeg") else decode_rgb8(v)
+            out[k] = EncodedImage(v, entropy=mark) if images != "host" and ext in ("jpg", "jpeg") else decode_rgb8(v)
         elif ext in ("pyd", "pickle"):
             out[k] = pickle.loads(v)
         elif ext in ("json", "jsn"):
@@ -162,11 +164,12 @@ class MultiviewWebDataset:
     ``defer_images=True`` leaves the pixels of a frame un-warped (``raw_image`` / ``affine`` / ``color_gain`` lists) so
     that ``collation_random_n_views`` can warp every view of the batch in one launch.  ``image_decode="device"`` keeps JPEG views
     encoded until that launch (``decode_record(images="device")``); a view that gets an occlusion patch is materialised on the
-    host, as its pixels are written there."""
+    host, as its pixels are written there.  ``image_decode="device-entropy"`` is the same with the Huffman decoding on the GPU too
+    (``transform.warp_views(jpeg_entropy="device")``)."""
 
     def __init__(self, cfg, data_preset=None, is_train=True, defer_images=False, rank=None, world=None, image_decode="host"):
-        if image_decode not in ("host", "device"):
-            raise ValueError("image_decode must be 'host' or 'device'")
+        if image_decode not in ("host", "device", "device-entropy"):
+            raise ValueError("image_decode must be 'host', 'device' or 'device-entropy'")
         self.cfg, self.is_train, self.defer_images, self.image_decode = cfg, is_train, defer_images, image_decode
         self.urls, self.data_split = cfg.URLS, cfg.DATA_SPLIT
         self.epoch_size = cfg.get("EPOCH_SIZE", None)

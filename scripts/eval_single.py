@@ -323,7 +323,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``), as ``evaluate`` does.
     ``image_decode``: ``"device"`` keeps the records' JPEG views encoded up to the batch's warp launch (Huffman decoding on host
     threads, reconstruction on the GPU, bit-equal to PIL; ``wds.EncodedImage``) and adds ``jpeg_device_fraction`` to the result: the
-    share of those views the device route took (the rest went through PIL).
+    share of those views the device route took (the rest went through PIL).  ``"device-entropy"``: the same with the Huffman
+    decoding on the GPU as well (``poem_jpeg_entropy_device``); a batch in which the device refuses a scan is redone on ``"device"``'s route.
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
     shards of the same record layout are written there first."""
     rank, _, world = pdist.env_world()
@@ -431,7 +432,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         res["benchmark"] = bench_scores.result()
     if inlier_acc is not None:
         res["dlt_inlier_fraction"] = inlier_acc.result()
-    if image_decode == "device":
+    if image_decode in ("device", "device-entropy"):
         counts = pk.transform.jpeg_counts()
         seen = counts["taken"] + counts["refused"]
         res["jpeg_device_fraction"] = counts["taken"] / seen if seen else None      # None: the shards hold no JPEG view
@@ -569,10 +570,11 @@ def build_cli():
                         help="add a \"benchmark\" block to the result line: the FreiHAND / HO3D leaderboard numbers -- mesh F@5 / F@15, raw "
                              "and Procrustes-aligned (PA_), the AUC of the aligned joints / vertices over 0..50 mm (pa_auc_j / pa_auc_v) "
                              "and the symmetric mean nearest-vertex distance (chamfer_mm) -- computed on the device.")
-    parser.add_argument("--image-decode", choices=("host", "device"), default=argparse.SUPPRESS,
+    parser.add_argument("--image-decode", choices=("host", "device", "device-entropy"), default=argparse.SUPPRESS,
                         help="with --shards: who decodes the records' JPEG views -- host (PIL, the default) or device (Huffman decoding on "
                              "host threads, inverse DCT / up-sampling / colour on the GPU, bit-equal to PIL; a stream the device route "
-                             "refuses falls back to PIL).  device adds jpeg_device_fraction to the result line.")
+                             "refuses falls back to PIL) or device-entropy (device, with the Huffman decoding on the GPU too).  Both device "
+                             "routes add jpeg_device_fraction to the result line.")
     return parser
 
 
