@@ -57,6 +57,7 @@
  *                             (lib/data_wds/multiview_wds.py:112-118) -- the image side of the input pipeline
  *   poem_rot6d_to_axis_angle  rot6d_to_aa of get_parametric_output (pt_metro_transformer.py:144-146, lib/utils/transform.py:448-466)
  *   poem_mano_lbs             manotorch ManoLayer.forward (pt_metro_transformer.py:120-124,147-148; ptEmb_head.py:732-736,886-892)
+ *   poem_mano_fit             MANO pose / shape / translation fitted to a mesh (upstream only offline: lib/fit/frame_fit/one_frame_fit.py)
  *   poem_render_mesh /        DrawingHandCallback's mesh overlay and 2-D skeleton (lib/utils/testing.py:101-192 -> OpenDRRenderer,
  *   poem_draw_skeleton /      lib/viztools/opendr_renderer.py:11-206, and draw_2d_skeleton, lib/viztools/draw.py:234-336): upstream renders on
  *   poem_project_points       the host through OpenGL, one view at a time; batch_cam_extr_transf + batch_cam_intr_projection in front of it
@@ -620,6 +621,40 @@ int poem_mano_lbs(const float* pose_aa, const float* betas, const void* table, i
  * caller-owned and must stay valid while attached; table = NULL detaches (the caller then runs its own layer and
  * poem_finalize_parametric).  POEM_E_UNSUPPORTED on a handle without PARAMETRIC_OUTPUT. */
 int poem_attach_mano(poem_handle_t h, const void* table, int center_idx);
+/* Fit MANO pose, shape and translation to a mesh (upstream only offline: lib/fit/frame_fit/one_frame_fit.py, hundreds of Adam
+ * steps per frame on the host through manotorch).  Levenberg-Marquardt with the analytic Jacobian; csrc/mano_fit.hip.
+ *   Unknowns per sample  x = (pose_aa[48], betas[10], tsl[3]), 61 in all.
+ *   Model  V(x) = the MANO mesh as stated above (csrc/mano.hip), NOT centred, plus tsl.  Rodrigues is the smooth exponential map
+ *     exp([aa]x), without poem_mano_lbs's +1e-8 (the two differ by about 1e-8 rad); value and derivative use their series below
+ *     |aa| = 1e-2, so a joint at exactly zero has the three generators as its derivative.
+ *   r = V(x) - target (2334 numbers);  c = sum r^2 + shape_reg |betas|^2 + pose_reg |pose_aa[3:]|^2;
+ *   g = J^T r, H = J^T J, with the regularisers' terms added (reg * x_p to g_p, reg to H_pp).
+ *   Start: x0 (batch,61) when given.  Otherwise: root rotation = the rigid, scale-free alignment of the zero-pose, zero-shape mesh
+ *     onto the target (the rotation of PAEval.align_w_scale's solve, taken to axis-angle through the quaternion with its largest
+ *     component first: finite at angle pi), fingers and betas 0, tsl = centroid of the target - centroid of the rotated mesh.
+ *     That solve handles no reflection (as upstream's alignment): for a mirrored target its orthogonal factor is improper and is
+ *     passed through the quaternion unchanged -- a finite start that is no alignment, left to the iteration.
+ *   Iteration, exactly `iters` times, mu = 1e-3 at first:  solve (H + mu D) dx = -g with D = max(diag H, 1e-12) by Cholesky;
+ *     evaluate c, g, H at x + dx; accept iff the new cost is strictly smaller (a NaN is never accepted); on accept
+ *     mu <- max(mu / 10, 1e-9), otherwise mu <- min(10 mu, 1e8) and x, g, H stay.  A pivot that is not positive or not finite
+ *     gives dx = 0, which the same rule rejects.
+ *   -> pose_aa (batch,48), betas (batch,10), tsl (batch,3) fp32; verts (batch,778,3) and joints (batch,21,3) = the model at the
+ *     result, rounded to fp32; cost (batch) fp64 = c at the result; accepted (batch) int32 = accepted steps; status (batch) int32:
+ *     0, or bit 0 = the target is not finite, bit 1 = the start (or its cost) is not finite.  A flagged sample returns its start
+ *     (zeros where the default start could not be formed), cost NaN, accepted 0, and touches no other sample.
+ *   fp32 inputs, every step fp64, no floating-point atomics, every sum in a fixed order: a sample's bits do not depend on its
+ *   batch or its position in it, and two calls give the same bits.  2 * iters + 4 launches on `stream`, no host synchronisation.
+ *   workspace: poem_mano_fit_workspace_bytes(batch) bytes, 8-byte aligned, caller-owned, need not be zeroed.  After the call its
+ *     head holds the solver's fp64 state, for diagnostics and tests: sample b's 3928 doubles begin at double 3928 * b --
+ *     x[61] at 0 (the result), the last candidate x + dx at 64, g[61] at 128, c at 192, mu at 193, H (61 x 61, row-major) at 200.
+ *   POEM_E_ARG (nothing launched, outputs untouched): iters outside 0..64, a negative or non-finite regulariser, a null required
+ *   pointer, batch < 0, a misaligned workspace; POEM_E_WORKSPACE: a short workspace; POEM_E_UNSUPPORTED: batch > 65535.
+ *   batch == 0 is POEM_OK without a launch.  Not built: 2-D keypoint / silhouette terms, joint targets, per-vertex weights,
+ *   PCA pose, left hands, a backward pass. */
+size_t poem_mano_fit_workspace_bytes(int batch);
+int poem_mano_fit(const void* table, const float* target_verts, const float* x0_or_null, int batch, int iters, float shape_reg,
+                  float pose_reg, void* workspace, size_t workspace_bytes, float* pose_aa, float* betas, float* tsl, float* verts,
+                  float* joints, double* cost, int32_t* accepted, int32_t* status, void* stream);
 /* Crop / warp / normalise every view of a batch in one launch (replaces the per-view host chain of
  * lib/utils/transform.py:153-170: cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT 0) -> colour jitter -> to_tensor ->
  * normalize(0.5, 1)).  src: the raw uint8 HxWx3 images back to back in one device blob; src_offsets (views) byte offset

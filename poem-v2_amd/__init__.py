@@ -16,6 +16,8 @@ from .transform import TRANSFORM, SimpleTransform3DMultiView, build_transform  #
 from .wds import MultiviewWebDataset, MixWebDataset, collation_random_n_views  # noqa: F401
 from .jpeg import EncodedImage  # noqa: F401
 from .mano import ManoLayer  # noqa: F401
+from . import fit  # noqa: F401
+from .fit import ManoFit, fit_mano  # noqa: F401
 from .hip import make_basis  # noqa: F401
 from .render import MeshRenderer, DrawingHandCallback, draw_skeleton, project_to_views, save_png  # noqa: F401
 from .losses import PoemLoss, LossMetric  # noqa: F401

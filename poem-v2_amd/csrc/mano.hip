@@ -30,20 +30,9 @@
 // blends its row of the 16 joint transforms and applies it.  Fixed summation order per output: a sample's result does not
 // depend on the batch (tested bit-exact).
 #include "common.h"
+#include "mano_layout.h"
 
 namespace {
-constexpr int NV = 778, NJ = 16, NPOSE = 135, NBETA = 10;
-constexpr int VP = 832;                    // vertices padded to 13 tiles of 64
-constexpr int K4 = 37;                     // 148 / 4 coefficient groups (10 shape + 135 pose + 3 zero)
-constexpr int OFF_VT = 0;                  // [3][VP]
-constexpr int OFF_D = OFF_VT + 3 * VP;     // [K4][3][VP][4]
-constexpr int OFF_W = OFF_D + K4 * 3 * VP * 4;   // [NJ][VP]
-constexpr int OFF_JT = OFF_W + NJ * VP;    // [48]
-constexpr int OFF_JSD = OFF_JT + 48;       // [48][10]
-constexpr int TABLE_FLOATS = OFF_JSD + 48 * NBETA;
-__constant__ int kTips[5] = {745, 317, 444, 556, 673};
-__constant__ int kOrder[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
-const int kOrderHost[21] = {0, 13, 14, 15, 16, 1, 2, 3, 17, 4, 5, 6, 18, 10, 11, 12, 19, 7, 8, 9, 20};
 
 __device__ __forceinline__ void rodrigues(const float* aa, float* R) {
   const float x = aa[0] + 1e-8f, y = aa[1] + 1e-8f, z = aa[2] + 1e-8f;

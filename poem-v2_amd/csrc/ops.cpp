@@ -595,6 +595,27 @@ int poem_mano_lbs(const float* pose_aa, const float* betas, const void* table, i
   return POEM_OK;
 }
 
+size_t poem_mano_fit_workspace_bytes(int batch) {
+  if (batch <= 0) return 0;
+  return sizeof(double) * poem_mano_fit_workspace_doubles_impl(batch);
+}
+
+int poem_mano_fit(const void* table, const float* target_verts, const float* x0_or_null, int batch, int iters, float shape_reg,
+                  float pose_reg, void* workspace, size_t workspace_bytes, float* pose_aa, float* betas, float* tsl, float* verts,
+                  float* joints, double* cost, int32_t* accepted, int32_t* status, void* stream) {
+  if (batch < 0 || iters < 0 || iters > 64) return POEM_E_ARG;
+  if (!(shape_reg >= 0.f) || !(pose_reg >= 0.f) || !std::isfinite(shape_reg) || !std::isfinite(pose_reg)) return POEM_E_ARG;
+  if (batch == 0) return POEM_OK;
+  if (!table || !target_verts || !workspace || !pose_aa || !betas || !tsl || !verts || !joints || !cost || !accepted || !status)
+    return POEM_E_ARG;
+  if (batch > 65535) return POEM_E_UNSUPPORTED;                              // one grid row per sample
+  if (((uintptr_t)workspace & 7u) != 0) return POEM_E_ARG;
+  if (workspace_bytes < poem_mano_fit_workspace_bytes(batch)) return POEM_E_WORKSPACE;
+  HIPCHK(poem_launch_mano_fit((const float*)table, target_verts, x0_or_null, batch, iters, shape_reg, pose_reg, (double*)workspace,
+                              pose_aa, betas, tsl, verts, joints, cost, accepted, status, (hipStream_t)stream));
+  return POEM_OK;
+}
+
 int poem_warp_affine(const uint8_t* src, const int64_t* src_offsets, const int32_t* src_hw, const double* m_inv,
                      const double* gain, float* out_f32, uint8_t* out_u8, int views, int out_h, int out_w, void* stream) {
   if (!src || !src_offsets || !src_hw || !m_inv || (!out_f32 && !out_u8) || views <= 0 || out_h <= 0 || out_w <= 0)

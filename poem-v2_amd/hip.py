@@ -134,6 +134,8 @@ SIGNATURES = {
     "poem_mano_prepare": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "poem_mano_lbs": (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     "poem_attach_mano": (_i, [_vp, _vp, _i]),
+    "poem_mano_fit_workspace_bytes": (_sz, [_i]),
+    "poem_mano_fit": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "poem_profile_read_stage": (_i, [_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_f)]),
     "poem_warp_affine": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "poem_pck_accumulate": (_i, [_vp, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp]),

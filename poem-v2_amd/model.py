@@ -13,7 +13,9 @@ from . import resnet  # noqa: F401  (registers ResNet18 / ResNet34 / ResNet50)
 from .backbone import HRNet  # noqa: F401
 from .builder import BACKBONE, MODEL, CN, build_head
 from .decode import FEAT_SIZES, FeatureDecoders
+from .fit import MAX_ITERS as MAX_FIT_ITERS, fit_mano
 from .losses import LossMetric, PoemLoss
+from .mano import ManoLayer
 from .triangulation import triangulate_reference_joints
 
 
@@ -74,6 +76,19 @@ class PtEmbedMultiviewStereoV2:
             raise ValueError(f"DLT_CONFIDENCE {self.dlt_confidence!r}: expected one of {DLT_CONFIDENCE_MODES}")
         if not self.dlt_inlier_px > 0 or not 0 <= self.dlt_refine_iters <= 16:
             raise ValueError(f"DLT_INLIER_PX = {self.dlt_inlier_px} must be > 0 and DLT_REFINE_ITERS = {self.dlt_refine_iters} in 0..16")
+        # FIT_MANO (absent / false by default; no upstream counterpart in the forward: lib/fit/frame_fit/one_frame_fit.py fits offline):
+        # MANO pose, shape and translation of the last layer's predicted vertices, fitted on the device after the forward (fit.py);
+        # FIT_MANO_ITERS Levenberg-Marquardt iterations (0..64).  Needs the MANO assets (MANO_ASSETS here or at the head, or
+        # set_mano_assets() before construction ends -- an importable manotorch counts).
+        self.fit_mano = bool(cfg.get("FIT_MANO", False))
+        self.fit_mano_iters = int(cfg.get("FIT_MANO_ITERS", 8))
+        self._fit_layer = self._fit_layer_assets = None
+        if self.fit_mano:
+            if not 0 <= self.fit_mano_iters <= MAX_FIT_ITERS:
+                raise ValueError(f"FIT_MANO_ITERS = {self.fit_mano_iters} must be in 0..{MAX_FIT_ITERS}")
+            if self.ptEmb_head._mano_assets is None:
+                raise ValueError("FIT_MANO needs the MANO assets: set MANO_ASSETS (an .npz of v_template, shapedirs, posedirs, "
+                                 "J_regressor, weights) at the model or its head")
         self.decoders = None
         # optional LOSS node (POEM.py:41-45,125-146): the loss VALUE of a forward; absent -> compute_loss raises, nothing else changes
         self.loss = None
@@ -172,7 +187,21 @@ class PtEmbedMultiviewStereoV2:
             preds["pred_joints_conf"] = conf
         if inlier is not None:
             preds.update(pred_joints_inlier=inlier, pred_joints_reproj=reproj)
+        if self.fit_mano:
+            fit = fit_mano(self._mano_fit_layer(), v.contiguous(), iters=self.fit_mano_iters)
+            preds.update(pred_mano_pose=fit.pose_aa, pred_mano_shape=fit.betas, pred_mano_tsl=fit.tsl, pred_mano_verts=fit.verts,
+                         pred_mano_status=fit.status)
         return preds
+
+    def _mano_fit_layer(self):
+        """The uncentred layer the fit reads its table from, built once from the head's assets (again if they were replaced)."""
+        assets = self.ptEmb_head._mano_assets
+        if assets is None:
+            raise RuntimeError("FIT_MANO: the head has no MANO assets any more")
+        if self._fit_layer is None or self._fit_layer_assets is not assets:
+            self._fit_layer = ManoLayer.from_arrays(**assets, center_idx=None, device=self.device)
+            self._fit_layer_assets = assets
+        return self._fit_layer
 
     def testing_step(self, batch, step_idx=0, **kwargs):
         return self._forward_impl(batch, mode="test", **kwargs)

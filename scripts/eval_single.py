@@ -180,12 +180,55 @@ class InlierFraction:
         return n / total if total else None
 
 
+class ManoFitStats:
+    """``--fit-mano``: the mean vertex distance between the fitted and the predicted mesh (mm), the number of flagged samples and,
+    where the records carry ground-truth fits, the mean absolute betas error -- sums on the device, read once at the end."""
+
+    def __init__(self, device):
+        self.acc = torch.zeros(5, dtype=torch.float64, device=device)   # (sum of distances, vertices, flagged, sum |dbeta|, betas)
+
+    def feed(self, fit_verts, pred_verts, status, betas=None, gt_betas=None):
+        ok = (status == 0)
+        d = torch.linalg.norm(fit_verts.double() - pred_verts.double(), dim=-1)[ok]
+        self.acc[0] += d.sum()
+        self.acc[1] += d.numel()
+        self.acc[2] += (~ok).sum()
+        if gt_betas is not None:
+            e = (betas.double() - gt_betas.double()).abs()[ok]
+            self.acc[3] += e.sum()
+            self.acc[4] += e.numel()
+
+    def result(self):
+        a = self.acc.tolist()
+        res = {"mano_fit_residual_mm": a[0] / a[1] * 1e3 if a[1] else None, "mano_fit_flagged": int(a[2])}
+        if a[4]:
+            res["mano_fit_betas_mae"] = a[3] / a[4]
+        return res
+
+
+def master_rows(batch):
+    """row of each sample's master view in the per-view arrays of a collated batch"""
+    views = np.asarray(batch["cam_view_num"]).astype(np.int64)
+    first = np.concatenate([[0], np.cumsum(views)[:-1]]).astype(np.int64)
+    master = batch["master_id"]
+    master = master.cpu().numpy() if torch.is_tensor(master) else np.asarray(master)
+    return torch.as_tensor(first + master.astype(np.int64).reshape(-1))
+
+
 def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, batch_size=2, seed=0, verbose=True,
              pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, mano_assets=None,
-             benchmark_scores=False, dlt_inlier_px=8.0, dlt_refine=0):
+             benchmark_scores=False, dlt_inlier_px=8.0, dlt_refine=0, fit_mano_iters=None):
     """``draw``: a ``DrawingHandCallback`` (rank 0, ``--draw --faces``) called with every batch.  This scope has no images: the panels
-    show the meshes and skeletons over mid-grey views.  ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``)."""
+    show the meshes and skeletons over mid-grey views.  ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``).
+    ``fit_mano_iters``: not None fits MANO pose / shape / translation to every predicted mesh (``pk.fit_mano``, needs ``mano_assets``)
+    and adds ``mano_fit_residual_mm`` / ``mano_fit_flagged`` to the result."""
     rank, _, world = pdist.env_world()
+    fit_layer = fit_acc = None
+    if fit_mano_iters is not None:
+        if not mano_assets:
+            raise SystemExit("--fit-mano needs the MANO assets: pass --mano-assets FILE.npz")
+        fit_layer = pk.ManoLayer(pk.mano.normalise_mano_assets(mano_assets), center_idx=None, device=device)
+        fit_acc = ManoFitStats(device)
     if dlt_confidence != "off" and not pyramid:
         raise SystemExit("--dlt-confidence reads the heat-map stage's output: it needs --pyramid or --shards (this scope starts "
                          "behind the heat-map stage)")
@@ -272,6 +315,10 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
             pck_v.feed({"pred_verts_3d": preds[-1, :, 21:]}, {"master_verts_3d": gt[:, 21:]})
             if bench_scores is not None:
                 bench_scores.feed(preds[-1, :, :21], gt[:, :21], preds[-1, :, 21:], gt[:, 21:])
+            if fit_acc is not None:
+                pv = preds[-1, :, 21:].contiguous()
+                fitted = pk.fit_mano(fit_layer, pv, iters=fit_mano_iters)
+                fit_acc.feed(fitted.verts, pv, fitted.status)
             if draw is not None:                           # rendering, the copy and the PNG files stay out of samples/s
                 torch.cuda.synchronize(device)
                 t_d = time.perf_counter()
@@ -301,6 +348,8 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
         res["benchmark"] = bench_scores.result()
     if inlier_acc is not None:
         res["dlt_inlier_fraction"] = inlier_acc.result()
+    if fit_acc is not None:
+        res.update(fit_acc.result())
     return res
 
 
@@ -310,7 +359,7 @@ BACKBONE_TYPES = {"hrnet": "HRNet", "resnet18": "ResNet18", "resnet34": "ResNet3
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
                     n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
                     mano_assets=None, backbone_engine="torch", backbone="hrnet", benchmark_scores=False, dlt_inlier_px=8.0,
-                    dlt_refine=0, image_decode="host"):
+                    dlt_refine=0, image_decode="host", fit_mano_iters=None):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -325,6 +374,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     threads, reconstruction on the GPU, bit-equal to PIL; ``wds.EncodedImage``) and adds ``jpeg_device_fraction`` to the result: the
     share of those views the device route took (the rest went through PIL).  ``"device-entropy"``: the same with the Huffman
     decoding on the GPU as well (``poem_jpeg_entropy_device``); a batch in which the device refuses a scan is redone on ``"device"``'s route.
+    ``fit_mano_iters``: not None sets the model keys FIT_MANO / FIT_MANO_ITERS (needs ``mano_assets``); the result gains
+    ``mano_fit_residual_mm``, ``mano_fit_flagged`` and, where the records carry ``mano_shape``, ``mano_fit_betas_mae``.
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
     shards of the same record layout are written there first."""
     rank, _, world = pdist.env_world()
@@ -351,6 +402,12 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         model_node["LOSS"] = loss_node(cfg)
     if mano_assets:
         model_node["MANO_ASSETS"] = mano_assets
+    fit_acc = None
+    if fit_mano_iters is not None:
+        if not mano_assets:
+            raise SystemExit("--fit-mano needs the MANO assets: pass --mano-assets FILE.npz")
+        model_node["FIT_MANO"], model_node["FIT_MANO_ITERS"] = True, int(fit_mano_iters)
+        fit_acc = ManoFitStats(device)
     if backbone_engine != "torch":
         model_node["BACKBONE"] = {"ENGINE": backbone_engine}
     if backbone != "hrnet":
@@ -395,6 +452,13 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
             inlier_acc.feed(preds["pred_joints_inlier"])
         if bench_scores is not None:
             bench_scores.feed(preds["pred_joints_3d"], gj, preds["pred_verts_3d"], gv)
+        if fit_acc is not None:
+            gt_betas = None
+            if batch.get("mano_shape", None) is not None:              # per view; the master view's row is the sample's
+                ms = batch["mano_shape"]
+                ms = (ms if torch.is_tensor(ms) else torch.as_tensor(np.asarray(ms))).reshape(-1, 10).to(device)
+                gt_betas = ms[master_rows(batch).to(device)]
+            fit_acc.feed(preds["pred_mano_verts"], preds["pred_verts_3d"], preds["pred_mano_status"], preds["pred_mano_shape"], gt_betas)
         if losses is not None:                             # one launch + finalize, sums stay on the device (POEM.py:476,483 upstream)
             model.loss_metric.feed(model.compute_loss(preds, batch)[1], len(frames))
         if draw is not None:                               # kept out of samples/s, as in evaluate()
@@ -432,6 +496,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         res["benchmark"] = bench_scores.result()
     if inlier_acc is not None:
         res["dlt_inlier_fraction"] = inlier_acc.result()
+    if fit_acc is not None:
+        res.update(fit_acc.result())
     if image_decode in ("device", "device-entropy"):
         counts = pk.transform.jpeg_counts()
         seen = counts["taken"] + counts["refused"]
@@ -444,6 +510,10 @@ def main(args):
     check_losses_args(args)
     mano_assets = getattr(args, "mano_assets", None)          # (absent from a build_parser() namespace)
     robust = dict(dlt_inlier_px=getattr(args, "dlt_inlier_px", 8.0), dlt_refine=getattr(args, "dlt_refine", 0))
+    if getattr(args, "fit_mano", False):                     # (both absent from a build_parser() namespace)
+        robust["fit_mano_iters"] = int(getattr(args, "fit_mano_iters", 8))
+        if not 0 <= robust["fit_mano_iters"] <= 64:
+            raise SystemExit(f"--fit-mano-iters {robust['fit_mano_iters']}: expected 0..64")
     if args.cfg and os.path.exists(args.cfg):
         with open(args.cfg, "r") as f:
             cfg = yaml.load(f, Loader=yaml.FullLoader)
@@ -570,6 +640,12 @@ def build_cli():
                         help="add a \"benchmark\" block to the result line: the FreiHAND / HO3D leaderboard numbers -- mesh F@5 / F@15, raw "
                              "and Procrustes-aligned (PA_), the AUC of the aligned joints / vertices over 0..50 mm (pa_auc_j / pa_auc_v) "
                              "and the symmetric mean nearest-vertex distance (chamfer_mm) -- computed on the device.")
+    parser.add_argument("--fit-mano", action="store_true", default=argparse.SUPPRESS,
+                        help="fit MANO pose, shape and translation to every predicted mesh on the device (Levenberg-Marquardt, "
+                             "poem_v2_amd.fit_mano; model keys FIT_MANO / FIT_MANO_ITERS).  Needs --mano-assets.  The result line gains "
+                             "mano_fit_residual_mm (mean vertex distance fitted - predicted), mano_fit_flagged and, where the records "
+                             "carry ground-truth fits, mano_fit_betas_mae.")
+    parser.add_argument("--fit-mano-iters", type=int, default=argparse.SUPPRESS, help="--fit-mano: LM iterations, 0..64 (default 8).")
     parser.add_argument("--image-decode", choices=("host", "device", "device-entropy"), default=argparse.SUPPRESS,
                         help="with --shards: who decodes the records' JPEG views -- host (PIL, the default) or device (Huffman decoding on "
                              "host threads, inverse DCT / up-sampling / colour on the GPU, bit-equal to PIL; a stream the device route "
