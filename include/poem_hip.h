@@ -58,6 +58,7 @@
  *   poem_rot6d_to_axis_angle  rot6d_to_aa of get_parametric_output (pt_metro_transformer.py:144-146, lib/utils/transform.py:448-466)
  *   poem_mano_lbs             manotorch ManoLayer.forward (pt_metro_transformer.py:120-124,147-148; ptEmb_head.py:732-736,886-892)
  *   poem_mano_fit             MANO pose / shape / translation fitted to a mesh (upstream only offline: lib/fit/frame_fit/one_frame_fit.py)
+ *   poem_mano_fit_terms       ... and to 3-D joint targets and 2-D keypoints in N calibrated views per sample (what upstream's fitter fits)
  *   poem_render_mesh /        DrawingHandCallback's mesh overlay and 2-D skeleton (lib/utils/testing.py:101-192 -> OpenDRRenderer,
  *   poem_draw_skeleton /      lib/viztools/opendr_renderer.py:11-206, and draw_2d_skeleton, lib/viztools/draw.py:234-336): upstream renders on
  *   poem_project_points       the host through OpenGL, one view at a time; batch_cam_extr_transf + batch_cam_intr_projection in front of it
@@ -649,12 +650,63 @@ int poem_attach_mano(poem_handle_t h, const void* table, int center_idx);
  *     x[61] at 0 (the result), the last candidate x + dx at 64, g[61] at 128, c at 192, mu at 193, H (61 x 61, row-major) at 200.
  *   POEM_E_ARG (nothing launched, outputs untouched): iters outside 0..64, a negative or non-finite regulariser, a null required
  *   pointer, batch < 0, a misaligned workspace; POEM_E_WORKSPACE: a short workspace; POEM_E_UNSUPPORTED: batch > 65535.
- *   batch == 0 is POEM_OK without a launch.  Not built: 2-D keypoint / silhouette terms, joint targets, per-vertex weights,
+ *   batch == 0 is POEM_OK without a launch.  2-D keypoint terms and joint targets: poem_mano_fit_terms below, of which this call
+ *   is the case "term M alone, mesh_weight 1" (the same kernels, the same bits).  Not built: silhouette terms, per-vertex weights,
  *   PCA pose, left hands, a backward pass. */
 size_t poem_mano_fit_workspace_bytes(int batch);
 int poem_mano_fit(const void* table, const float* target_verts, const float* x0_or_null, int batch, int iters, float shape_reg,
                   float pose_reg, void* workspace, size_t workspace_bytes, float* pose_aa, float* betas, float* tsl, float* verts,
                   float* joints, double* cost, int32_t* accepted, int32_t* status, void* stream);
+/* The fit with up to three data terms: the mesh (M), 3-D joint targets (J) and 2-D keypoints in N calibrated views per sample (K).
+ * Unknowns, model, regularisers, the iteration (mu, D, accept iff strictly smaller, a failed pivot = rejected), the fp64 rule and
+ * the fixed-order sums are exactly poem_mano_fit's.  P_j(x), j = 0..20, is the fit's own `joints` output: the 16 chain joints and
+ * the five tip vertices in the 21-joint hand order, uncentred, plus tsl (the order of pred_joints_3d / pred_joints_uv).
+ *   c = mesh_weight sum_v |V_v(x) - target_v|^2                                      (M, present iff target_verts != NULL)
+ *     + sum_j w3[b,j] |P_j(x) - joints3d[b,j]|^2                                     (J, present iff joints3d != NULL)
+ *     + sum_{view n of sample b} sum_j w2[n,j] |(pi_n(P_j(x)) - kp[n,j]) / image_scale|^2     (K, present iff keypoints != NULL)
+ *     + shape_reg |betas|^2 + pose_reg |pose_aa[3:]|^2,        g and H the Gauss-Newton ones of these rows.
+ *   pi_n(p): p_cam = inv(cam_extr[n]) p (batch_cam_extr_transf; the 4x4 inverted in fp64 in the kernel), h = cam_intr[n] p_cam with
+ *     the full 3x3, (u, v) = (h_x, h_y) / h_z (batch_cam_intr_projection) -- the convention of poem_loss_terms and
+ *     poem_project_points, without upstream's |z| < 1e-7 -> 1e-7 clamp, which has no derivative worth following.
+ *   Depth: a keypoint of positive weight whose camera-frame depth p_cam.z is <= POEM_FIT_ZMIN makes that candidate's cost +inf, so
+ *     the accept rule rejects it; at the start it sets status bit 2 and the sample returns its start like the other flags.
+ *   Views are ragged: view_offsets (batch + 1, int32, on the device; the host never reads it) -- sample b owns views
+ *     [view_offsets[b], view_offsets[b+1]), which may be one view or none; indices are clamped into [0, total_views].
+ *   Weights: an entry of weight 0 contributes nothing and is not read into the arithmetic (compare and select, never 0 * value:
+ *     missing keypoints are commonly NaN); a view whose 21 weights are all 0 leaves every bit of the call as if it were absent
+ *     (its camera is not read either).  A weight that is negative, NaN or infinite sets status bit 0; so does a non-finite mesh
+ *     target, and a non-finite joint target, keypoint or camera under a positive weight.
+ *   Start: x0 when given; otherwise with M the default of poem_mano_fit; otherwise with J the same rigid rule on the 21 zero-pose,
+ *     zero-shape joints against joints3d (a joint there of weight 0 or not finite sets status bit 1).  K alone needs x0.
+ *   status: bit 0 an input is not finite / a weight is not valid, bit 1 the start (or its cost) is not finite, bit 2 (value 4) the
+ *     start has a positive-weight keypoint at depth <= POEM_FIT_ZMIN.  Bit 2 is set by the joint-term kernel at the first
+ *     evaluation (the joints at the start need the whole model), which a sample flagged with bit 0 or 1 never reaches: bit 2
+ *     never comes together with them.  The mesh kernel still runs once for such a sample.
+ *   Upstream (one_frame_fit.py) minimises lambda_reproj mean_{n,j}(w |delta / scale|^2) + 5 * 0.1 |betas|^2: the mean is the constant
+ *     factor 1 / (21 views_b) per sample, so its data term is term K with keypoint_weight = lambda_reproj w / (21 views_b) and
+ *     shape_reg = 0.5.  Its quaternion-norm and anatomical axis losses are NOT built, nor its Adam iteration.
+ *   Kernels (csrc/mano_fit.hip): the joint-term kernel, one block per sample, runs next to the mesh kernel at every evaluation and
+ *     writes one more slot of sums; terms J and K are accumulated per joint over the views in order (a 3x3 matrix, a 3-vector and a
+ *     scalar), never as a per-view Jacobian.  Launches on `stream`, no host synchronisation: 2 + (iters + 1) (1 + [M] + [J or K]),
+ *     i.e. 3 * iters + 5 with M and a joint term, 2 * iters + 4 with one of the two.
+ *   workspace: poem_mano_fit_terms_workspace_bytes(batch); its head is poem_mano_fit's (3928 doubles per sample, same offsets).
+ *   POEM_E_ARG (nothing launched, outputs untouched): no term present; term K with any of keypoints, keypoint_weight, cam_intr,
+ *     cam_extr, view_offsets NULL or total_views < 0; a weight array without its values (or joints3d without joints3d_weight);
+ *     mesh_weight negative or not finite (read with M only); image_scale not > 0 or not finite (read with K only); K alone without
+ *     x0; a NULL `terms`; and everything poem_mano_fit refuses.  POEM_E_UNSUPPORTED: total_views > 65535, batch > 65535. */
+#define POEM_FIT_ZMIN 1e-3        /* metres */
+typedef struct {
+  const float* target_verts;   float mesh_weight;              /* (batch,778,3) or NULL                        */
+  const float* joints3d;       const float* joints3d_weight;   /* (batch,21,3), (batch,21), or both NULL       */
+  const float* keypoints;      const float* keypoint_weight;   /* (total_views,21,2), (total_views,21)         */
+  const float* cam_intr;       const float* cam_extr;          /* (total_views,3,3), (total_views,4,4)         */
+  const int32_t* view_offsets; int total_views;                /* (batch+1) on the device; term K needs all six */
+  float image_scale;                                           /* > 0, finite                                  */
+} poem_mano_fit_terms_t;
+size_t poem_mano_fit_terms_workspace_bytes(int batch);
+int poem_mano_fit_terms(const void* table, const poem_mano_fit_terms_t* terms, const float* x0_or_null, int batch, int iters,
+                        float shape_reg, float pose_reg, void* workspace, size_t workspace_bytes, float* pose_aa, float* betas,
+                        float* tsl, float* verts, float* joints, double* cost, int32_t* accepted, int32_t* status, void* stream);
 /* Crop / warp / normalise every view of a batch in one launch (replaces the per-view host chain of
  * lib/utils/transform.py:153-170: cv2.warpAffine(INTER_LINEAR, BORDER_CONSTANT 0) -> colour jitter -> to_tensor ->
  * normalize(0.5, 1)).  src: the raw uint8 HxWx3 images back to back in one device blob; src_offsets (views) byte offset

@@ -212,9 +212,11 @@ hipError_t poem_launch_mano_lbs(const float* pose, const float* betas, const flo
                                 int center_idx, hipStream_t s);
 size_t poem_mano_table_floats_impl();
 size_t poem_mano_fit_workspace_doubles_impl(int B);
-hipError_t poem_launch_mano_fit(const float* table, const float* target, const float* x0, int B, int iters, float shape_reg,
-                                float pose_reg, double* ws, float* pose, float* betas, float* tsl, float* verts, float* joints,
-                                double* cost, int32_t* accepted, int32_t* status, hipStream_t s);
+size_t poem_mano_fit_terms_workspace_doubles_impl(int B);
+hipError_t poem_launch_mano_fit_terms(const float* table, const poem_mano_fit_terms_t* terms, int joint_slot, const float* x0,
+                                      int B, int iters, float shape_reg, float pose_reg, double* ws, float* pose, float* betas,
+                                      float* tsl, float* verts, float* joints, double* cost, int32_t* accepted, int32_t* status,
+                                      hipStream_t s);
 hipError_t poem_launch_param_rows(const float* verts, const float* joints, float* out_last, int B, int Q, hipStream_t s);
 hipError_t poem_launch_compose_weight(const float* A, const float* Bm, float* out, int N, int Cm, int K, hipStream_t s);
 hipError_t poem_launch_compose_bias(const float* A, const float* b1, const float* b2, float* out, int N, int Cm,

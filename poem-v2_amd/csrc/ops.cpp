@@ -611,8 +611,42 @@ int poem_mano_fit(const void* table, const float* target_verts, const float* x0_
   if (batch > 65535) return POEM_E_UNSUPPORTED;                              // one grid row per sample
   if (((uintptr_t)workspace & 7u) != 0) return POEM_E_ARG;
   if (workspace_bytes < poem_mano_fit_workspace_bytes(batch)) return POEM_E_WORKSPACE;
-  HIPCHK(poem_launch_mano_fit((const float*)table, target_verts, x0_or_null, batch, iters, shape_reg, pose_reg, (double*)workspace,
-                              pose_aa, betas, tsl, verts, joints, cost, accepted, status, (hipStream_t)stream));
+  poem_mano_fit_terms_t terms = {};             // term M alone, weight 1: the same launches on the 49-slot workspace
+  terms.target_verts = target_verts;
+  terms.mesh_weight = 1.f;
+  HIPCHK(poem_launch_mano_fit_terms((const float*)table, &terms, 0, x0_or_null, batch, iters, shape_reg, pose_reg, (double*)workspace,
+                                    pose_aa, betas, tsl, verts, joints, cost, accepted, status, (hipStream_t)stream));
+  return POEM_OK;
+}
+
+size_t poem_mano_fit_terms_workspace_bytes(int batch) {
+  if (batch <= 0) return 0;
+  return sizeof(double) * poem_mano_fit_terms_workspace_doubles_impl(batch);
+}
+
+int poem_mano_fit_terms(const void* table, const poem_mano_fit_terms_t* terms, const float* x0_or_null, int batch, int iters,
+                        float shape_reg, float pose_reg, void* workspace, size_t workspace_bytes, float* pose_aa, float* betas,
+                        float* tsl, float* verts, float* joints, double* cost, int32_t* accepted, int32_t* status, void* stream) {
+  if (batch < 0 || iters < 0 || iters > 64 || !terms) return POEM_E_ARG;
+  if (!(shape_reg >= 0.f) || !(pose_reg >= 0.f) || !std::isfinite(shape_reg) || !std::isfinite(pose_reg)) return POEM_E_ARG;
+  const bool M = terms->target_verts != nullptr, J = terms->joints3d != nullptr, K = terms->keypoints != nullptr;
+  if (!M && !J && !K) return POEM_E_ARG;
+  if (M && (!(terms->mesh_weight >= 0.f) || !std::isfinite(terms->mesh_weight))) return POEM_E_ARG;
+  if (J != (terms->joints3d_weight != nullptr)) return POEM_E_ARG;
+  if (!K && terms->keypoint_weight) return POEM_E_ARG;
+  if (K) {
+    if (!terms->keypoint_weight || !terms->cam_intr || !terms->cam_extr || !terms->view_offsets || terms->total_views < 0)
+      return POEM_E_ARG;
+    if (!(terms->image_scale > 0.f) || !std::isfinite(terms->image_scale)) return POEM_E_ARG;
+    if (!M && !J && !x0_or_null) return POEM_E_ARG;                            // keypoints alone give no start
+  }
+  if (batch == 0) return POEM_OK;
+  if (!table || !workspace || !pose_aa || !betas || !tsl || !verts || !joints || !cost || !accepted || !status) return POEM_E_ARG;
+  if (batch > 65535 || (K && terms->total_views > 65535)) return POEM_E_UNSUPPORTED;
+  if (((uintptr_t)workspace & 7u) != 0) return POEM_E_ARG;
+  if (workspace_bytes < poem_mano_fit_terms_workspace_bytes(batch)) return POEM_E_WORKSPACE;
+  HIPCHK(poem_launch_mano_fit_terms((const float*)table, terms, 1, x0_or_null, batch, iters, shape_reg, pose_reg, (double*)workspace,
+                                    pose_aa, betas, tsl, verts, joints, cost, accepted, status, (hipStream_t)stream));
   return POEM_OK;
 }
 

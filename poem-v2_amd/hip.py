@@ -43,6 +43,15 @@ class PoemFuseTerm(ctypes.Structure):
                 ("row_stride", ctypes.c_int32), ("offset", ctypes.c_int32), ("shift", ctypes.c_int32)]
 
 
+class PoemManoFitTerms(ctypes.Structure):
+    """include/poem_hip.h poem_mano_fit_terms_t"""
+    _fields_ = [("target_verts", ctypes.c_void_p), ("mesh_weight", ctypes.c_float), ("joints3d", ctypes.c_void_p),
+                ("joints3d_weight", ctypes.c_void_p), ("keypoints", ctypes.c_void_p), ("keypoint_weight", ctypes.c_void_p),
+                ("cam_intr", ctypes.c_void_p), ("cam_extr", ctypes.c_void_p), ("view_offsets", ctypes.c_void_p),
+                ("total_views", ctypes.c_int32), ("image_scale", ctypes.c_float)]
+
+
+FIT_ZMIN = 1e-3              # include/poem_hip.h POEM_FIT_ZMIN
 LOSS_NTERMS = 10             # include/poem_hip.h POEM_LOSS_NTERMS
 
 _vp, _i, _f, _sz, _i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_int64
@@ -136,6 +145,9 @@ SIGNATURES = {
     "poem_attach_mano": (_i, [_vp, _vp, _i]),
     "poem_mano_fit_workspace_bytes": (_sz, [_i]),
     "poem_mano_fit": (_i, [_vp, _vp, _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "poem_mano_fit_terms_workspace_bytes": (_sz, [_i]),
+    "poem_mano_fit_terms": (_i, [_vp, ctypes.POINTER(PoemManoFitTerms), _vp, _i, _i, _f, _f, _vp, _sz, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                 _vp, _vp]),
     "poem_profile_read_stage": (_i, [_vp, _i, ctypes.POINTER(_i), ctypes.POINTER(_f)]),
     "poem_warp_affine": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _vp]),
     "poem_pck_accumulate": (_i, [_vp, _vp, _i, _i, ctypes.c_double, ctypes.c_double, _i, _vp, _vp, _vp, _vp, _vp]),

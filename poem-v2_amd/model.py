@@ -40,6 +40,17 @@ def build_img_backbone(cfg, device):
     return net
 
 
+def fit_keypoint_weight(cfg):
+    """The model key FIT_MANO_KEYPOINTS -> weight_2d (0.0: off).  It must be a finite number >= 0 and needs FIT_MANO."""
+    w2d = cfg.get("FIT_MANO_KEYPOINTS", None)
+    if w2d is not None and (isinstance(w2d, (bool, str)) or not isinstance(w2d, (int, float)) or not np.isfinite(w2d) or w2d < 0):
+        raise ValueError(f"FIT_MANO_KEYPOINTS = {w2d!r} must be a finite number >= 0 (the weight of the 2-D term; 0: off)")
+    w2d = float(w2d or 0.0)
+    if w2d > 0 and not bool(cfg.get("FIT_MANO", False)):
+        raise ValueError("FIT_MANO_KEYPOINTS needs FIT_MANO")
+    return w2d
+
+
 @MODEL.register_module()
 class PtEmbedMultiviewStereoV2:
 
@@ -83,6 +94,11 @@ class PtEmbedMultiviewStereoV2:
         self.fit_mano = bool(cfg.get("FIT_MANO", False))
         self.fit_mano_iters = int(cfg.get("FIT_MANO_ITERS", 8))
         self._fit_layer = self._fit_layer_assets = None
+        # FIT_MANO_KEYPOINTS (a float weight_2d; absent or 0: off): the fit also pulls its 21 joints onto the forward's own 2-D joints
+        # in every view (fit.py term K): weight = weight_2d x pred_joints_conf (where the DLT mode reads confidences) x
+        # pred_joints_inlier (where it is "ransac"), image_scale = max(H, W), the batch's cameras.  Its useful range on real data
+        # has NOT been measured.
+        self.fit_mano_keypoints = fit_keypoint_weight(cfg)
         if self.fit_mano:
             if not 0 <= self.fit_mano_iters <= MAX_FIT_ITERS:
                 raise ValueError(f"FIT_MANO_ITERS = {self.fit_mano_iters} must be in 0..{MAX_FIT_ITERS}")
@@ -187,7 +203,18 @@ class PtEmbedMultiviewStereoV2:
             preds["pred_joints_conf"] = conf
         if inlier is not None:
             preds.update(pred_joints_inlier=inlier, pred_joints_reproj=reproj)
-        if self.fit_mano:
+        if self.fit_mano and self.fit_mano_keypoints > 0:
+            w2 = torch.full(uv_pred.shape[:2], self.fit_mano_keypoints, dtype=torch.float32, device=uv_pred.device)
+            if conf is not None:
+                w2 = w2 * conf
+            if inlier is not None:
+                w2 = torch.where(inlier, w2, torch.zeros_like(w2))
+            fit = fit_mano(self._mano_fit_layer(), v.contiguous(), iters=self.fit_mano_iters, keypoints=uv_pred.float().contiguous(),
+                           keypoint_weights=w2, cam_intr=K.float().contiguous(), cam_extr=T.float().contiguous(),
+                           cam_view_num=views, image_scale=float(max(H, W)))
+            preds.update(pred_mano_pose=fit.pose_aa, pred_mano_shape=fit.betas, pred_mano_tsl=fit.tsl, pred_mano_verts=fit.verts,
+                         pred_mano_status=fit.status, pred_mano_joints=fit.joints, pred_mano_keypoint_weight=w2)
+        elif self.fit_mano:
             fit = fit_mano(self._mano_fit_layer(), v.contiguous(), iters=self.fit_mano_iters)
             preds.update(pred_mano_pose=fit.pose_aa, pred_mano_shape=fit.betas, pred_mano_tsl=fit.tsl, pred_mano_verts=fit.verts,
                          pred_mano_status=fit.status)

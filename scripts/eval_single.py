@@ -185,7 +185,8 @@ class ManoFitStats:
     where the records carry ground-truth fits, the mean absolute betas error -- sums on the device, read once at the end."""
 
     def __init__(self, device):
-        self.acc = torch.zeros(5, dtype=torch.float64, device=device)   # (sum of distances, vertices, flagged, sum |dbeta|, betas)
+        # (sum of distances, vertices, flagged, sum |dbeta|, betas, sum of reprojection distances in pixels, keypoints)
+        self.acc = torch.zeros(7, dtype=torch.float64, device=device)
 
     def feed(self, fit_verts, pred_verts, status, betas=None, gt_betas=None):
         ok = (status == 0)
@@ -198,11 +199,24 @@ class ManoFitStats:
             self.acc[3] += e.sum()
             self.acc[4] += e.numel()
 
-    def result(self):
+    def feed_reproj(self, fit_joints, uv, weight, cam_intr, cam_extr, views, status):
+        """``--fit-mano-keypoints``: pixel distance between the fitted joints' projections and the 2-D joints, over the entries of
+        positive weight of unflagged samples"""
+        views = [int(v) for v in views]
+        proj = pk.render.project_to_views(fit_joints.contiguous(), cam_intr.float().contiguous(), cam_extr.float().contiguous(), views)
+        ok = torch.repeat_interleave(status == 0, torch.as_tensor(views, device=status.device))
+        use = (weight > 0) & ok[:, None]
+        d = torch.linalg.norm(proj.double() - uv.double(), dim=-1)[use]
+        self.acc[5] += d.sum()
+        self.acc[6] += d.numel()
+
+    def result(self, reproj=False):
         a = self.acc.tolist()
         res = {"mano_fit_residual_mm": a[0] / a[1] * 1e3 if a[1] else None, "mano_fit_flagged": int(a[2])}
         if a[4]:
             res["mano_fit_betas_mae"] = a[3] / a[4]
+        if reproj:
+            res["mano_fit_reproj_px"] = a[5] / a[6] if a[6] else None
         return res
 
 
@@ -217,11 +231,13 @@ def master_rows(batch):
 
 def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, batch_size=2, seed=0, verbose=True,
              pyramid=False, template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, mano_assets=None,
-             benchmark_scores=False, dlt_inlier_px=8.0, dlt_refine=0, fit_mano_iters=None):
+             benchmark_scores=False, dlt_inlier_px=8.0, dlt_refine=0, fit_mano_iters=None, fit_mano_keypoints=0.0):
     """``draw``: a ``DrawingHandCallback`` (rank 0, ``--draw --faces``) called with every batch.  This scope has no images: the panels
     show the meshes and skeletons over mid-grey views.  ``benchmark_scores``: add the ``"benchmark"`` block (``BenchmarkScores``).
     ``fit_mano_iters``: not None fits MANO pose / shape / translation to every predicted mesh (``pk.fit_mano``, needs ``mano_assets``)
-    and adds ``mano_fit_residual_mm`` / ``mano_fit_flagged`` to the result."""
+    and adds ``mano_fit_residual_mm`` / ``mano_fit_flagged`` to the result.  ``fit_mano_keypoints`` > 0: the fit also takes the 2-D
+    joints the reference joints were triangulated from, in every view, with that weight (times the confidences and the inlier mask
+    where the DLT mode has them), and the result gains ``mano_fit_reproj_px``."""
     rank, _, world = pdist.env_world()
     fit_layer = fit_acc = None
     if fit_mano_iters is not None:
@@ -305,6 +321,11 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
                 rj = triangulate_reference_joints(uv, metas["cam_intr"], metas["cam_extr"], views)
             else:                                        # single-view samples take the given joints (POEM.py:282-283)
                 rj = b["reference_joints"].to(device)
+            kp_conf, kp_inl = None, None
+            if min(views) >= 2 and dlt_confidence == "ransac":
+                kp_inl = inl
+            elif min(views) >= 2 and dlt_confidence != "off":
+                kp_conf = conf
             preds = head(mlvl_feat, metas, rj)["all_coords_preds"]
             g = torch.Generator().manual_seed(seed * 7919 + s)
             gt = (b["reference_joints"][:, 9:10] + 0.05 * torch.randn(len(views), 799, 3, generator=g)).to(device)
@@ -317,7 +338,16 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
                 bench_scores.feed(preds[-1, :, :21], gt[:, :21], preds[-1, :, 21:], gt[:, 21:])
             if fit_acc is not None:
                 pv = preds[-1, :, 21:].contiguous()
-                fitted = pk.fit_mano(fit_layer, pv, iters=fit_mano_iters)
+                if fit_mano_keypoints > 0:
+                    w2 = torch.full(uv.shape[:2], float(fit_mano_keypoints), dtype=torch.float32, device=device)
+                    w2 = w2 if kp_conf is None else w2 * kp_conf
+                    w2 = w2 if kp_inl is None else torch.where(kp_inl, w2, torch.zeros_like(w2))
+                    cams = (metas["cam_intr"].float().contiguous(), metas["cam_extr"].float().contiguous())
+                    fitted = pk.fit_mano(fit_layer, pv, iters=fit_mano_iters, keypoints=uv.float().contiguous(), keypoint_weights=w2,
+                                         cam_intr=cams[0], cam_extr=cams[1], cam_view_num=views, image_scale=256.0)
+                    fit_acc.feed_reproj(fitted.joints, uv, w2, cams[0], cams[1], views, fitted.status)
+                else:
+                    fitted = pk.fit_mano(fit_layer, pv, iters=fit_mano_iters)
                 fit_acc.feed(fitted.verts, pv, fitted.status)
             if draw is not None:                           # rendering, the copy and the PNG files stay out of samples/s
                 torch.cuda.synchronize(device)
@@ -349,7 +379,7 @@ def evaluate(cfg, view_range, model_type, device, reload=None, epoch_size=64, ba
     if inlier_acc is not None:
         res["dlt_inlier_fraction"] = inlier_acc.result()
     if fit_acc is not None:
-        res.update(fit_acc.result())
+        res.update(fit_acc.result(reproj=fit_mano_keypoints > 0))
     return res
 
 
@@ -359,7 +389,7 @@ BACKBONE_TYPES = {"hrnet": "HRNet", "resnet18": "ResNet18", "resnet34": "ResNet3
 def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, reload=None, epoch_size=16, batch_size=2,
                     n_cams=8, raw_size=(640, 480), template=None, dlt_confidence="off", dlt_threshold=0.5, draw=None, losses=None,
                     mano_assets=None, backbone_engine="torch", backbone="hrnet", benchmark_scores=False, dlt_inlier_px=8.0,
-                    dlt_refine=0, image_decode="host", fit_mano_iters=None):
+                    dlt_refine=0, image_decode="host", fit_mano_iters=None, fit_mano_keypoints=0.0):
     """Images -> metrics from record shards (SURVEY 8f N4 in front of the model): ``MultiviewWebDataset`` over the URLS of the
     edited config (tar records: ``image_<i>.png|jpg`` + ``label.pyd``), the per-view crop / warp / normalise on the
     device (one launch per batch), ``collation_random_n_views``, then the model-level caller
@@ -376,6 +406,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     decoding on the GPU as well (``poem_jpeg_entropy_device``); a batch in which the device refuses a scan is redone on ``"device"``'s route.
     ``fit_mano_iters``: not None sets the model keys FIT_MANO / FIT_MANO_ITERS (needs ``mano_assets``); the result gains
     ``mano_fit_residual_mm``, ``mano_fit_flagged`` and, where the records carry ``mano_shape``, ``mano_fit_betas_mae``.
+    ``fit_mano_keypoints`` > 0 sets the model key FIT_MANO_KEYPOINTS; the result gains ``mano_fit_reproj_px``.
     The dataset tars are not available offline: when ``shard_dir`` holds no shard of the dataset's name, seeded synthetic
     shards of the same record layout are written there first."""
     rank, _, world = pdist.env_world()
@@ -407,6 +438,8 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
         if not mano_assets:
             raise SystemExit("--fit-mano needs the MANO assets: pass --mano-assets FILE.npz")
         model_node["FIT_MANO"], model_node["FIT_MANO_ITERS"] = True, int(fit_mano_iters)
+        if fit_mano_keypoints > 0:
+            model_node["FIT_MANO_KEYPOINTS"] = float(fit_mano_keypoints)
         fit_acc = ManoFitStats(device)
     if backbone_engine != "torch":
         model_node["BACKBONE"] = {"ENGINE": backbone_engine}
@@ -459,6 +492,10 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
                 ms = (ms if torch.is_tensor(ms) else torch.as_tensor(np.asarray(ms))).reshape(-1, 10).to(device)
                 gt_betas = ms[master_rows(batch).to(device)]
             fit_acc.feed(preds["pred_mano_verts"], preds["pred_verts_3d"], preds["pred_mano_status"], preds["pred_mano_shape"], gt_betas)
+            if "pred_mano_joints" in preds:
+                fit_acc.feed_reproj(preds["pred_mano_joints"], preds["pred_joints_uv"], preds["pred_mano_keypoint_weight"],
+                                    batch["target_cam_intr"].reshape(-1, 3, 3).to(device), batch["target_cam_extr"].reshape(-1, 4, 4).to(device),
+                                    batch["cam_view_num"], preds["pred_mano_status"])
         if losses is not None:                             # one launch + finalize, sums stay on the device (POEM.py:476,483 upstream)
             model.loss_metric.feed(model.compute_loss(preds, batch)[1], len(frames))
         if draw is not None:                               # kept out of samples/s, as in evaluate()
@@ -497,7 +534,7 @@ def evaluate_shards(cfg, view_range, model_type, device, shard_dir, dataset, rel
     if inlier_acc is not None:
         res["dlt_inlier_fraction"] = inlier_acc.result()
     if fit_acc is not None:
-        res.update(fit_acc.result())
+        res.update(fit_acc.result(reproj=fit_mano_keypoints > 0))
     if image_decode in ("device", "device-entropy"):
         counts = pk.transform.jpeg_counts()
         seen = counts["taken"] + counts["refused"]
@@ -514,6 +551,11 @@ def main(args):
         robust["fit_mano_iters"] = int(getattr(args, "fit_mano_iters", 8))
         if not 0 <= robust["fit_mano_iters"] <= 64:
             raise SystemExit(f"--fit-mano-iters {robust['fit_mano_iters']}: expected 0..64")
+    if hasattr(args, "fit_mano_keypoints"):                  # (absent from the namespace unless given)
+        w2d = float(args.fit_mano_keypoints)
+        if not getattr(args, "fit_mano", False) or not np.isfinite(w2d) or w2d < 0:
+            raise SystemExit(f"--fit-mano-keypoints {w2d}: needs --fit-mano and a finite weight >= 0")
+        robust["fit_mano_keypoints"] = w2d
     if args.cfg and os.path.exists(args.cfg):
         with open(args.cfg, "r") as f:
             cfg = yaml.load(f, Loader=yaml.FullLoader)
@@ -646,6 +688,11 @@ def build_cli():
                              "mano_fit_residual_mm (mean vertex distance fitted - predicted), mano_fit_flagged and, where the records "
                              "carry ground-truth fits, mano_fit_betas_mae.")
     parser.add_argument("--fit-mano-iters", type=int, default=argparse.SUPPRESS, help="--fit-mano: LM iterations, 0..64 (default 8).")
+    parser.add_argument("--fit-mano-keypoints", type=float, default=argparse.SUPPRESS, metavar="W",
+                        help="--fit-mano: also fit the 21 joints to the 2-D joints of every view with weight W (times the confidences / the "
+                             "RANSAC inlier mask where the DLT mode has them; model key FIT_MANO_KEYPOINTS).  The result line gains "
+                             "mano_fit_reproj_px: the mean pixel distance between the fitted joints' projections and those 2-D joints.  "
+                             "The useful range of W on real data has not been measured.")
     parser.add_argument("--image-decode", choices=("host", "device", "device-entropy"), default=argparse.SUPPRESS,
                         help="with --shards: who decodes the records' JPEG views -- host (PIL, the default) or device (Huffman decoding on "
                              "host threads, inverse DCT / up-sampling / colour on the GPU, bit-equal to PIL; a stream the device route "
