@@ -128,7 +128,7 @@ __device__ __forceinline__ void gemm16(const __amdgpu_buffer_rsrc_t wrs, int wba
   }
   if constexpr (RU * T16 <= 2 && KCH % 8 == 0) {
     // small tiles (one or two units of 16 rows: a chunk is 2 RU T16 MFMAs of 32 cycles -- 128 to 256 cycles): weight fragments
-    // seven chunks ahead, as lds_gemm.h does for its small tiles and for the same reason (a small batch's tile is a latency chain)
+    // seven chunks ahead, as lds_gemm.h's X4_W8 schedule and for the same reason (a small batch's tile is a latency chain)
     // (32-row fragment images only: these tiles take the ring on native images while POEM_C16_RING_MAX >= 2)
     static_assert(!NAT, "gemm16's small-tile branch reads 32-row fragment images, not native 16x16x4 ones");
     float4 ar[8][T16];
@@ -158,10 +158,8 @@ __device__ __forceinline__ void gemm16(const __amdgpu_buffer_rsrc_t wrs, int wba
 #define C16_LOADW(A, KCI)                                                                                     \
   {                                                                                                           \
     const int kq_ = min((KCI), KCH - 1);                                                                      \
-    _Pragma("unroll") for (int t = 0; t < T16; ++t) {                                                         \
-      if constexpr (NAT) A[t] = frag_load_nat<NAT>(wrs, (t & 1) ? loff1 : loff0, wbase + (t >> 1) * tile_stride + kq_ * 1024); \
-      else A[t] = frag_load_nat<NAT>(wrs, (t & 1) ? loff1 : loff0, wbase + (t >> 1) * tile_stride + kq_ * 1024); \
-    }                                                                                                         \
+    _Pragma("unroll") for (int t = 0; t < T16; ++t)                                                           \
+      A[t] = frag_load_nat<NAT>(wrs, (t & 1) ? loff1 : loff0, wbase + (t >> 1) * tile_stride + kq_ * 1024);   \
   }
   C16_LOADW(a0, 0)
   C16_READX(xa, 0)

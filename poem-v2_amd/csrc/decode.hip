@@ -488,6 +488,20 @@ __global__ __launch_bounds__(512) void conv3x3_lds_kernel(Conv3Args A) {
 // to a stride == 16 mod 32 floats so that the two channel planes a 32-lane group reads fall on disjoint banks.
 // Result layout: lane (g, j) holds output channels 16c + 4g .. + 3 of pixel j.
 typedef float f32x2v __attribute__((ext_vector_type(2)));
+// What the three 16x16x4 staged kernels (conv3x3_lds16_kernel, conv3x3_s2_kernel, conv3x3_s2p_kernel) share, as text: the weight
+// fragments of one tap for all CT16 channel tiles (pack_conv3x3_m16_kernel's images through `wrs`), and one tap's 4 * CT16 MFMAs
+// on two units of 16 pixels (B[0], B[1]: channel g; B[2], B[3]: channel 4 + g).  Each kernel keeps its own tap-offset rule
+// (LOADB) and its own STEP (staging hook, ring shape).  Macros, not functions: as __forceinline__ function templates the same
+// text compiled to different register numbering in every instantiation (LABNOTES).  They read wrs, lane, KC, CT16 and acc
+// of the kernel they expand in.
+#define POEM_M16_LOADW(AW, TAP, CC)                                                                             \
+  _Pragma("unroll") for (int c = 0; c < CT16; ++c)                                                              \
+    AW[c] = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(wrs, lane * 8, ((c * 9 + (TAP)) * KC + (CC)) * 512, 0));
+#define POEM_M16_MMA(AW, B)                                                                                     \
+  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
+    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(AW[c][0], B[u], acc[c][u], 0, 0, 0); \
+  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
+    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(AW[c][1], B[2 + u], acc[c][u], 0, 0, 0);
 template <int CT16, bool UPCAT, int RW = 0, bool POOL = false, bool EX = false>
 __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Args A) {
   constexpr bool ROWSG = RW != 0;
@@ -534,25 +548,17 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
   // fragments and the four B operands of tap t + 1 are requested before tap t's 4 * CT16 MFMAs issue.
   f32x2v wa[CT16], wb[CT16];
   float ba[4], bb[4];
-#define POEM_T16_LOADW(A, TAP, CC)                                                                              \
-  _Pragma("unroll") for (int c = 0; c < CT16; ++c)                                                              \
-    A[c] = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(wrs, lane * 8, ((c * 9 + (TAP)) * KC + (CC)) * 512, 0));
 #define POEM_T16_LOADB(B, TAP)                                                                                  \
   {                                                                                                             \
     const int toff_ = ((TAP) / 3) * Wp + ((TAP) % 3);                                                           \
     B[0] = tb[boff[0] + toff_]; B[1] = tb[boff[1] + toff_];                                                     \
     B[2] = tb[boff[0] + 4 * tstride + toff_]; B[3] = tb[boff[1] + 4 * tstride + toff_];                         \
   }
-#define POEM_T16_MMA(A, B)                                                                                      \
-  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
-    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[c][0], B[u], acc[c][u], 0, 0, 0); \
-  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
-    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(A[c][1], B[2 + u], acc[c][u], 0, 0, 0);
 #define POEM_T16_STEP(CUR_A, CUR_B, NXT_A, NXT_B, TAP)                                                          \
-  POEM_T16_LOADW(NXT_A, (TAP) + 1, cc) POEM_T16_LOADB(NXT_B, (TAP) + 1)                                         \
+  POEM_M16_LOADW(NXT_A, (TAP) + 1, cc) POEM_T16_LOADB(NXT_B, (TAP) + 1)                                         \
   if constexpr (NEXT != 0 && (TAP) < SG::MAXLD) sg.template load_k<NEXT, ((TAP) < SG::MAXLD ? (TAP) : 0)>();    \
   __builtin_amdgcn_sched_barrier(0);                                                                            \
-  POEM_T16_MMA(CUR_A, CUR_B)                                                                                    \
+  POEM_M16_MMA(CUR_A, CUR_B)                                                                                    \
   __builtin_amdgcn_sched_barrier(0);
   // one chunk; NEXT = kind of the chunk staged meanwhile (0: none, 1: plain input / skip tensor, 2: interpolated part)
   auto chunk = [&](auto next_tag, const int cc) {
@@ -564,16 +570,16 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
     POEM_T16_STEP(wa, ba, wb, bb, 0) POEM_T16_STEP(wb, bb, wa, ba, 1) POEM_T16_STEP(wa, ba, wb, bb, 2) POEM_T16_STEP(wb, bb, wa, ba, 3)
     POEM_T16_STEP(wa, ba, wb, bb, 4) POEM_T16_STEP(wb, bb, wa, ba, 5) POEM_T16_STEP(wa, ba, wb, bb, 6) POEM_T16_STEP(wb, bb, wa, ba, 7)
     // last tap: the next chunk's first weight fragments ride behind it (its B operands wait for the barrier)
-    { const int ccn = min(cc + 1, KC - 1); POEM_T16_LOADW(wb, 0, ccn) }
+    { const int ccn = min(cc + 1, KC - 1); POEM_M16_LOADW(wb, 0, ccn) }
     __builtin_amdgcn_sched_barrier(0);
-    POEM_T16_MMA(wa, ba)
+    POEM_M16_MMA(wa, ba)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int c = 0; c < CT16; ++c) wa[c] = wb[c];
     if constexpr (NEXT != 0) { sg.template finish_k<NEXT>(); sg.store(tile + ((cc + 1) & 1) * 8 * tstride, tid); }
     __syncthreads();
   };
-  POEM_T16_LOADW(wa, 0, 0)
+  POEM_M16_LOADW(wa, 0, 0)
   {
     const int n_up = UPCAT ? A.Ca / 8 : 0;         // chunks [0, n_up) are interpolated, [n_up, KC) plain / skip tensor
     int cc = 0;
@@ -581,9 +587,7 @@ __global__ __launch_bounds__(512, RW ? 4 : 2) void conv3x3_lds16_kernel(Conv3Arg
     for (; cc + 1 < KC; ++cc) chunk(std::integral_constant<int, 1>{}, cc);
     chunk(std::integral_constant<int, 0>{}, cc);
   }
-#undef POEM_T16_LOADW
 #undef POEM_T16_LOADB
-#undef POEM_T16_MMA
 #undef POEM_T16_STEP
   // epilogue: lane (g, j) holds channels 16c + 4g + e of pixel (unit u, j)
   const int Ho = A.H, Wo = A.W;
@@ -701,27 +705,19 @@ __global__ __launch_bounds__(512, 4) void conv3x3_s2_kernel(Conv3Args A) {
   }
   f32x2v wa[CT16], wb[CT16];
   float ba[4], bb[4];
-#define POEM_S2_LOADW(AW, TAP, CC)                                                                              \
-  _Pragma("unroll") for (int c = 0; c < CT16; ++c)                                                              \
-    AW[c] = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(wrs, lane * 8, ((c * 9 + (TAP)) * KC + (CC)) * 512, 0));
 #define POEM_S2_LOADB(B, TAP)                                                                                   \
   {                                                                                                             \
     const int toff_ = ((TAP) / 3) * 2 * RS + (((TAP) % 3) & 1) * RS + (((TAP) % 3) >> 1);                       \
     B[0] = tb[boff[0] + toff_]; B[1] = tb[boff[1] + toff_];                                                     \
     B[2] = tb[boff[0] + 4 * tstride + toff_]; B[3] = tb[boff[1] + 4 * tstride + toff_];                         \
   }
-#define POEM_S2_MMA(AW, B)                                                                                      \
-  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
-    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(AW[c][0], B[u], acc[c][u], 0, 0, 0); \
-  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
-    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(AW[c][1], B[2 + u], acc[c][u], 0, 0, 0);
   // staging requests of the next chunk: two per tap (vmcnt retires in order: a burst in front of the taps would stand
   // between every tap and its weight fragments)
 #define POEM_S2_STEP(CUR_A, CUR_B, NXT_A, NXT_B, TAP)                                                           \
-  POEM_S2_LOADW(NXT_A, (TAP) + 1, cc) POEM_S2_LOADB(NXT_B, (TAP) + 1)                                           \
+  POEM_M16_LOADW(NXT_A, (TAP) + 1, cc) POEM_S2_LOADB(NXT_B, (TAP) + 1)                                          \
   if constexpr (NEXT != 0) { POEM_S2_DMA(2 * (TAP), cc + 1, (cc + 1) & 1) POEM_S2_DMA(2 * (TAP) + 1, cc + 1, (cc + 1) & 1) }  \
   __builtin_amdgcn_sched_barrier(0);                                                                            \
-  POEM_S2_MMA(CUR_A, CUR_B)                                                                                     \
+  POEM_M16_MMA(CUR_A, CUR_B)                                                                                    \
   __builtin_amdgcn_sched_barrier(0);
   auto chunk = [&](auto next_tag, const int cc) {
     constexpr int NEXT = decltype(next_tag)::value;
@@ -730,26 +726,24 @@ __global__ __launch_bounds__(512, 4) void conv3x3_s2_kernel(Conv3Args A) {
     __builtin_amdgcn_sched_barrier(0);
     POEM_S2_STEP(wa, ba, wb, bb, 0) POEM_S2_STEP(wb, bb, wa, ba, 1) POEM_S2_STEP(wa, ba, wb, bb, 2) POEM_S2_STEP(wb, bb, wa, ba, 3)
     POEM_S2_STEP(wa, ba, wb, bb, 4) POEM_S2_STEP(wb, bb, wa, ba, 5) POEM_S2_STEP(wa, ba, wb, bb, 6) POEM_S2_STEP(wb, bb, wa, ba, 7)
-    { const int ccn = min(cc + 1, KC - 1); POEM_S2_LOADW(wb, 0, ccn) }
+    { const int ccn = min(cc + 1, KC - 1); POEM_M16_LOADW(wb, 0, ccn) }
     if constexpr (NEXT != 0) { POEM_S2_DMA(16, cc + 1, (cc + 1) & 1) POEM_S2_DMA(17, cc + 1, (cc + 1) & 1) }
     __builtin_amdgcn_sched_barrier(0);
-    POEM_S2_MMA(wa, ba)
+    POEM_M16_MMA(wa, ba)
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int c = 0; c < CT16; ++c) wa[c] = wb[c];
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");       // this wave's LDS-DMA of the next chunk has landed
     __syncthreads();
   };
-  POEM_S2_LOADW(wa, 0, 0)
+  POEM_M16_LOADW(wa, 0, 0)
   {
     int cc = 0;
     for (; cc + 1 < KC; ++cc) chunk(std::integral_constant<int, 1>{}, cc);
     chunk(std::integral_constant<int, 0>{}, cc);
   }
 #undef POEM_S2_DMA
-#undef POEM_S2_LOADW
 #undef POEM_S2_LOADB
-#undef POEM_S2_MMA
 #undef POEM_S2_STEP
   // epilogue: lane (g, j) holds channels 80 cgrp + 16c + 4g + e of output pixel (unit u, j)
   const ConvMap plain(A.Cout, Ho, Wo);
@@ -840,9 +834,6 @@ __global__ __launch_bounds__(64 * (PXB * CG + 1)) void conv3x3_s2p_kernel(Conv3A
   f32x2v w0[CT16], w1[CT16], w2[CT16];
   float ba[4], bb[4];
   f32x4 acc[CT16][2];
-#define POEM_S2P_LOADW(AW, TAP, CC)                                                                             \
-  _Pragma("unroll") for (int c = 0; c < CT16; ++c)                                                              \
-    AW[c] = __builtin_bit_cast(f32x2v, __builtin_amdgcn_raw_buffer_load_b64(wrs, lane * 8, ((c * 9 + (TAP)) * KC + (CC)) * 512, 0));
 #define POEM_S2P_LOADB(B, TAP)                                                                                  \
   {                                                                                                             \
     const int toff_ = ((TAP) / 3) * W + (TAP) % 3;                                                              \
@@ -852,20 +843,15 @@ __global__ __launch_bounds__(64 * (PXB * CG + 1)) void conv3x3_s2p_kernel(Conv3A
       B[0] = opx[0] ? B[0] : 0.f; B[1] = opx[1] ? B[1] : 0.f; B[2] = opx[0] ? B[2] : 0.f; B[3] = opx[1] ? B[3] : 0.f; \
     }                                                                                                           \
   }
-#define POEM_S2P_MMA(AW, B)                                                                                     \
-  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
-    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(AW[c][0], B[u], acc[c][u], 0, 0, 0); \
-  _Pragma("unroll") for (int u = 0; u < 2; ++u)                                                                 \
-    _Pragma("unroll") for (int c = 0; c < CT16; ++c) acc[c][u] = __builtin_amdgcn_mfma_f32_16x16x4f32(AW[c][1], B[2 + u], acc[c][u], 0, 0, 0);
   // tap TAP on (CUR_W, CUR_B); the weights of tap TAP + 2 (of the next chunk past tap 6) and the operands of tap TAP + 1 requested
 #define POEM_S2P_STEP(CUR_W, CUR_B, NXT_W, NXT_B, TAP)                                                          \
-  POEM_S2P_LOADW(NXT_W, ((TAP) + 2) % 9, ((TAP) + 2 >= 9 ? ccn : cc))                                           \
+  POEM_M16_LOADW(NXT_W, ((TAP) + 2) % 9, ((TAP) + 2 >= 9 ? ccn : cc))                                           \
   if constexpr ((TAP) < 8) POEM_S2P_LOADB(NXT_B, (TAP) + 1)                                                     \
   __builtin_amdgcn_sched_barrier(0);                                                                            \
-  POEM_S2P_MMA(CUR_W, CUR_B)                                                                                    \
+  POEM_M16_MMA(CUR_W, CUR_B)                                                                                    \
   __builtin_amdgcn_sched_barrier(0);
-  POEM_S2P_LOADW(w0, 0, 0)
-  POEM_S2P_LOADW(w1, 1, 0)
+  POEM_M16_LOADW(w0, 0, 0)
+  POEM_M16_LOADW(w1, 1, 0)
   asm volatile("s_barrier" ::: "memory");                   // chunk 0 of the first tile has landed
   int f = 0, t = (int)blockIdx.x;
   for (int it = 0; it < my_tiles; ++it, t += (int)gridDim.x) {
@@ -930,11 +916,11 @@ __global__ __launch_bounds__(64 * (PXB * CG + 1)) void conv3x3_s2p_kernel(Conv3A
         }
     }
   }
-#undef POEM_S2P_LOADW
 #undef POEM_S2P_LOADB
-#undef POEM_S2P_MMA
 #undef POEM_S2P_STEP
 }
+#undef POEM_M16_LOADW
+#undef POEM_M16_MMA
 
 // Shapes conv3x3_s2_kernel takes: 80 / 160 / 320 output channels on 8-row output tiles of 32 / 16 / 8 columns.
 static int g_row_stager = 3;            // A/B switch: 0 = Conv3Stager for every fused-input convolution

@@ -190,7 +190,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sample_merge_kernel(SampleMer
     // ---- merge_net[0].0 + ReLU
     {
       f32x16 acc[TPW][P];
-      lds_gemm<KCH, XSP, P, TPW, true>(frag_rsrc(A.w0, CC4), __builtin_amdgcn_readfirstlane(wv * TPW * KCH * 1024), KCH * 1024, X0, acc, lane);
+      lds_gemm<KCH, XSP, P, TPW, true, lds_sched_chain(KCH, TPW, P)>(frag_rsrc(A.w0, CC4), __builtin_amdgcn_readfirstlane(wv * TPW * KCH * 1024), KCH * 1024, X0, acc, lane);
       bias_act<TPW, P>(acc, A.b0, wv * TPW, h, true);
       __syncthreads();                        // every wave is done reading the sampled tile
       acc_to_lds<TPW, P, XSP>(acc, X0, wv * TPW, 0, j, h);
@@ -202,7 +202,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sample_merge_kernel(SampleMer
     {
       const int t2 = wv / P, p2 = wv % P;
       f32x16 acc[1][1];
-      lds_gemm<KCH, XSP, 1, 1, true>(frag_rsrc(A.w1, CC4 / 2), __builtin_amdgcn_readfirstlane(t2 * KCH * 1024), KCH * 1024, X0 + 32 * p2, acc, lane);
+      lds_gemm<KCH, XSP, 1, 1, true, lds_sched_chain(KCH, 1, 1)>(frag_rsrc(A.w1, CC4 / 2), __builtin_amdgcn_readfirstlane(t2 * KCH * 1024), KCH * 1024, X0 + 32 * p2, acc, lane);
       bias_act<1, 1>(acc, A.b1, t2, h, false);
       const int jj = 32 * p2 + j;
       const size_t row = A.h2_tiled ? ((size_t)v * TPV + t) * XS + jj : (size_t)v * A.S + (size_t)(c0 + jj) * NSEG + seg;
@@ -232,7 +232,7 @@ __device__ __forceinline__ void tail_mlp(float* __restrict__ X0, const float4* _
   {
     const int tile0 = WIDE ? wv * TPWA : wv / P, col0 = WIDE ? 0 : 32 * (wv % P);
     f32x16 acc[TPWA][PA];
-    lds_gemm<KCH, XSP, PA, TPWA, true>(frag_rsrc(w0, (unsigned)(HALF * HALF * 4)), __builtin_amdgcn_readfirstlane(tile0 * KCH * 1024), KCH * 1024,
+    lds_gemm<KCH, XSP, PA, TPWA, true, lds_sched_chain(KCH, TPWA, PA)>(frag_rsrc(w0, (unsigned)(HALF * HALF * 4)), __builtin_amdgcn_readfirstlane(tile0 * KCH * 1024), KCH * 1024,
                                        X0 + col0, acc, lane);
     bias_act<TPWA, PA>(acc, b0, tile0, h, true);
     __syncthreads();
@@ -243,7 +243,7 @@ __device__ __forceinline__ void tail_mlp(float* __restrict__ X0, const float4* _
   {
     const int tile0 = wv * TPWB;
     f32x16 acc[TPWB][P];
-    lds_gemm<KCH, XSP, P, TPWB, true>(frag_rsrc(w1, (unsigned)(C * HALF * 4)), __builtin_amdgcn_readfirstlane(tile0 * KCH * 1024), KCH * 1024, X0, acc, lane);
+    lds_gemm<KCH, XSP, P, TPWB, true, lds_sched_chain(KCH, TPWB, P)>(frag_rsrc(w1, (unsigned)(C * HALF * 4)), __builtin_amdgcn_readfirstlane(tile0 * KCH * 1024), KCH * 1024, X0, acc, lane);
     bias_act<TPWB, P>(acc, b1, tile0, h, false);
     const float fn = (float)N;
 #pragma unroll
@@ -517,7 +517,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sample_group_kernel(SampleGro
       // ---- merge_net[0].0 + ReLU
       {
         f32x16 acc[TPW][P];
-        lds_gemm<KCH, XSP, P, TPW, true>(frag_rsrc(A.w0, CC4), __builtin_amdgcn_readfirstlane(wv * TPW * KCH * 1024), KCH * 1024, X0, acc, lane);
+        lds_gemm<KCH, XSP, P, TPW, true, lds_sched_chain(KCH, TPW, P)>(frag_rsrc(A.w0, CC4), __builtin_amdgcn_readfirstlane(wv * TPW * KCH * 1024), KCH * 1024, X0, acc, lane);
         bias_act<TPW, P>(acc, A.b0, wv * TPW, h, true);
         __syncthreads();                        // every wave is done reading the sampled tile
         acc_to_lds<TPW, P, XSP>(acc, X0, wv * TPW, 0, j, h);
@@ -533,7 +533,7 @@ __global__ __launch_bounds__(NW * 64, NW / 2) void sample_group_kernel(SampleGro
       // ---- merge_net[0].2: one (32-channel tile, column tile) of h per wave
       {
         f32x16 acc[1][1];
-        lds_gemm<KCH, XSP, 1, 1, true>(frag_rsrc(A.w1, CC4 / 2), __builtin_amdgcn_readfirstlane(t2 * KCH * 1024), KCH * 1024, X0 + 32 * p2, acc, lane);
+        lds_gemm<KCH, XSP, 1, 1, true, lds_sched_chain(KCH, 1, 1)>(frag_rsrc(A.w1, CC4 / 2), __builtin_amdgcn_readfirstlane(t2 * KCH * 1024), KCH * 1024, X0 + 32 * p2, acc, lane);
         bias_act<1, 1>(acc, A.b1, t2, h, false);
         const f32x16& hn = acc[0][0];
         if (n == 0) {

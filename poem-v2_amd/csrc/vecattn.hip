@@ -12,6 +12,7 @@
 // channel, registers = neighbours -- which makes the softmax over the 32 neighbours register-local (+1 exchange
 // between half-waves) and the v_j gathers coalesced.  Wave w owns output channel tiles [w*TPW, (w+1)*TPW).
 #include "common.h"
+#include "lds_gemm.h"
 #ifndef POEM_VA_XCD_SAMPLES
 #define POEM_VA_XCD_SAMPLES 1
 #endif
@@ -59,86 +60,13 @@ struct VecAttnArgs {
 // every CU hosts two blocks.  Used for speed only: a wrong parity costs overlap, never correctness.
 __device__ unsigned int va_cu_slot[8 * 256];
 
+// One C x C GEMM of the chain on lds_gemm.h's pipeline: wave wv's TPW channel tiles of the packed image Wp against X.
 template <int C, int P, int NW, int TPW, bool FLIP, bool INIT0 = true>
 __device__ __forceinline__ void chain_gemm(const float4* __restrict__ Wp, const float* __restrict__ X,
                                            f32x16 (&acc)[TPW][P], int wv, int lane) {
   constexpr int KC = C / 8;      // even for every supported C
-  constexpr int XS = 32 * P;
-  const int j = lane & 31, h = lane >> 5;
-  const __amdgpu_buffer_rsrc_t wrs = frag_rsrc(Wp, (unsigned)(C * C * 4));
-  const int wbase = __builtin_amdgcn_readfirstlane(wv) * TPW * KC * 1024;      // bytes, wave-uniform
-  const int loff = lane * 16;
-  const float* xc = X + (4 * h) * XS + j;
-  // Software pipeline with pinned order (sched_barrier): the weight fragments of chunk kc+1 are in flight while the MFMAs
-  // of chunk kc issue, and the LDS operands run a whole chunk ahead (below).  Left to itself hipcc sinks every load to
-  // its first use and the wave stalls on L2/LDS latency in front of each MFMA group.
-  float4 a0[TPW], a1[TPW];
-#define VA_LOADW(A, KCI)                                                                  \
-  {                                                                                       \
-    const int kq_ = min((KCI), KC - 1);                                                   \
-    _Pragma("unroll") for (int tp = 0; tp < TPW; ++tp) A[tp] = frag_load(wrs, loff, wbase + (tp * KC + kq_) * 1024); \
-  }
-#define VA_READX(XR, KCI, T)                                                              \
-  {                                                                                       \
-    const int kq_ = min((KCI), KC - 1);                                                   \
-    _Pragma("unroll") for (int p = 0; p < P; ++p) XR[p] = xc[(kq_ * 8 + (T)) * XS + 32 * p]; \
-  }
-  // INIT: the very first k-step takes its C operand from the inline constant 0 -- the accumulators are never zeroed
-  // with v_mov (64 VALU instructions per GEMM that would come straight out of the matrix pipe's time)
-#define VA_MMA(A, T, XR, INIT)                                                            \
-  _Pragma("unroll") for (int tp = 0; tp < TPW; ++tp) {                                    \
-    const float av = (&A[tp].x)[T];                                                       \
-    _Pragma("unroll") for (int p = 0; p < P; ++p) {                                       \
-      const f32x16 c_ = (INIT) ? zero16() : acc[tp][p];                                   \
-      acc[tp][p] = FLIP ? mfma32(XR[p], av, c_) : mfma32(av, XR[p], c_);                  \
-    }                                                                                     \
-  }
-  // X operands a whole chunk ahead (one register set per k-step of a chunk, re-requested right behind the MFMAs that read it)
-  float x0[P], x1[P], x2[P], x3[P];
-#define VA_CHUNK4(A, KCI, INIT)                                                             \
-  VA_MMA(A, 0, x0, INIT) __builtin_amdgcn_sched_barrier(0); VA_READX(x0, (KCI) + 1, 0) __builtin_amdgcn_sched_barrier(0);  \
-  VA_MMA(A, 1, x1, false) __builtin_amdgcn_sched_barrier(0); VA_READX(x1, (KCI) + 1, 1) __builtin_amdgcn_sched_barrier(0); \
-  VA_MMA(A, 2, x2, false) __builtin_amdgcn_sched_barrier(0); VA_READX(x2, (KCI) + 1, 2) __builtin_amdgcn_sched_barrier(0); \
-  VA_MMA(A, 3, x3, false) __builtin_amdgcn_sched_barrier(0); VA_READX(x3, (KCI) + 1, 3) __builtin_amdgcn_sched_barrier(0);
-  if constexpr (TPW <= 2) {
-  // weight fragments three chunks ahead (ring of four; 16 more VGPRs at TPW = 2 -- wider waves keep the ring of two)
-  static_assert(KC % 4 == 0, "C must be a multiple of 32");
-  float4 a2[TPW], a3[TPW];
-  VA_LOADW(a0, 0)
-  VA_READX(x0, 0, 0) VA_READX(x1, 0, 1) VA_READX(x2, 0, 2) VA_READX(x3, 0, 3)
-  VA_LOADW(a1, 1)
-  VA_LOADW(a2, 2)
-  __builtin_amdgcn_sched_barrier(0);
-#define VA_GROUP(KC0, INIT)                                                   \
-  VA_LOADW(a3, (KC0) + 3) __builtin_amdgcn_sched_barrier(0); VA_CHUNK4(a0, (KC0), INIT)      \
-  VA_LOADW(a0, (KC0) + 4) __builtin_amdgcn_sched_barrier(0); VA_CHUNK4(a1, (KC0) + 1, false) \
-  VA_LOADW(a1, (KC0) + 5) __builtin_amdgcn_sched_barrier(0); VA_CHUNK4(a2, (KC0) + 2, false) \
-  VA_LOADW(a2, (KC0) + 6) __builtin_amdgcn_sched_barrier(0); VA_CHUNK4(a3, (KC0) + 3, false)
-  VA_GROUP(0, INIT0)
-  for (int kc = 4; kc < KC; kc += 4) { VA_GROUP(kc, false) }
-#undef VA_GROUP
-  } else {
-  VA_LOADW(a0, 0)
-  VA_READX(x0, 0, 0) VA_READX(x1, 0, 1) VA_READX(x2, 0, 2) VA_READX(x3, 0, 3)
-  VA_LOADW(a1, 1)
-  __builtin_amdgcn_sched_barrier(0);
-  VA_CHUNK4(a0, 0, INIT0)
-  VA_LOADW(a0, 2)
-  __builtin_amdgcn_sched_barrier(0);
-  VA_CHUNK4(a1, 1, false)
-  for (int kc = 2; kc < KC; kc += 2) {
-    VA_LOADW(a1, kc + 1)
-    __builtin_amdgcn_sched_barrier(0);
-    VA_CHUNK4(a0, kc, false)
-    VA_LOADW(a0, kc + 2)
-    __builtin_amdgcn_sched_barrier(0);
-    VA_CHUNK4(a1, kc + 1, false)
-  }
-  }
-#undef VA_CHUNK4
-#undef VA_LOADW
-#undef VA_READX
-#undef VA_MMA
+  lds_gemm<KC, 32 * P, P, TPW, INIT0, lds_sched_vecattn(TPW), FLIP>(frag_rsrc(Wp, (unsigned)(C * C * 4)),
+      __builtin_amdgcn_readfirstlane(wv) * TPW * KC * 1024, KC * 1024, X, acc, lane);      // wbase: bytes, wave-uniform
 }
 
 // COMP (the decoder's form): W_g1 is linear, so W_g1 (q_i - k_j + pos_ij) + b_g1 = qg_i - kg_j + (W_g1 W_d2) h_ij with
